@@ -16,8 +16,14 @@ WORLD_SIZE / MASTER_* variables, started before anything loads the executor
 or touches a GPU (misaka_net_amd.dist.launch_ranks) -- forwards rank 0's
 line and exits non-zero if any rank fails.
 
-Prints ONE JSON line on rank 0 (keys per the driver contract + roofline +
-cpu_baseline).
+A plain run sets up, warms up, times the K steps, writes its outputs
+(--dump-outputs DIR) and prints the result line.  --full adds what takes runs
+of its own: the per-launch timing loop and the live VALU probe behind the
+roofline figures, the CPU baselines, and for N > 1 the end-to-end gather leg
+with its verification.
+
+Prints ONE JSON line on rank 0 (keys per the driver contract; with --full
+also roofline + cpu_baseline).
 """
 from __future__ import annotations
 
@@ -109,8 +115,33 @@ STACK_OPS_PER_LANE = {"c4": 2 * 64 * 8, "c4d256": 2 * 256 * 8, "c4d1024": 2 * 10
                       "t2_dyn_depth": 255, "t1_two_stacks": 255}
 
 
+DUMP_LANES = 1 << 20  # --dump-outputs: lanes written per rank (12 MiB of values + 8 MiB of indices)
+
+
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(path, rank, out, st, stats):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, as float .npy files.  `out` goes out as float64 (exact for int32),
+    the status bytes as float32; above DUMP_LANES lanes a fixed sample of them
+    (sorted lane indices drawn with SEED, the same from run to run) is
+    written, with the indices themselves in `lanes`.  `stats` are the device
+    counters the timed steps accumulated (retired, with output, finished, ...)
+    over every lane."""
+    lanes = out.numel()
+    if lanes > DUMP_LANES:
+        idx = np.sort(np.random.default_rng(SEED).choice(lanes, DUMP_LANES, replace=False))
+        sel = torch.from_numpy(idx).to(out.device)
+        out, st = out[sel], st[sel]
+    else:
+        idx = np.arange(lanes)
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in (("out", out.cpu().numpy().astype(np.float64)), ("status", st.cpu().numpy().astype(np.float32)),
+                    ("lanes", idx.astype(np.float64)), ("stats", stats.cpu().numpy().astype(np.float64))):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
 
 
 def usable_cpus():
@@ -423,6 +454,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-launch timing loop and VALU "
+                         "probe of the roofline figures, the CPU baselines (--no-cpu-baseline, --cpu-seconds, "
+                         "--refstruct-seconds) and, for N > 1, the end-to-end gather leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy: out "
+                         "(float64) and status (float32) of the lanes listed in lanes (every lane, or a fixed seeded "
+                         f"sample of {DUMP_LANES} of them), and stats, the device counters summed over the timed steps "
+                         "(rank r > 0 writes <name>_rank<r>.npy)")
     ap.add_argument("--sessions", type=int, default=0, metavar="N",
                     help="also time N stateful instances x 8 sequential /compute calls (row f2; reported as "
                          "sessions, never as value)")
@@ -551,23 +591,26 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
     kernel_s = e0.elapsed_time(e1) * 1e-3  # HIP events on the launch stream
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, out, st, stats)
 
-    # Average duration of one executor launch (the dominant kernel) for the
-    # roofline: HIP events around K launches on the launch stream.
-    k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    k0.record(stream)
-    for _ in range(args.steps):
-        step(False)
-    k1.record(stream)
-    torch.cuda.synchronize()
-    launch_s = k0.elapsed_time(k1) * 1e-3 / args.steps
+    launch_s, peak_meas = 0.0, None
+    if args.full:
+        # Average duration of one executor launch (the dominant kernel) for the
+        # roofline: HIP events around K launches on the launch stream.
+        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        k0.record(stream)
+        for _ in range(args.steps):
+            step(False)
+        k1.record(stream)
+        torch.cuda.synchronize()
+        launch_s = k0.elapsed_time(k1) * 1e-3 / args.steps
 
-    peak_meas = None
-    if rank == 0:
-        try:
-            peak_meas = valu_peak(sh)
-        except Exception as e:  # pragma: no cover
-            log("valu probe failed:", e)
+        if rank == 0:
+            try:
+                peak_meas = valu_peak(sh)
+            except Exception as e:  # pragma: no cover
+                log("valu probe failed:", e)
     peak = max(SPEC_LANE_OPS, peak_meas or 0.0)
 
     # per-rank -> whole job (max time over ranks, summed work)
@@ -585,7 +628,7 @@ def main():
     # section 8 row e), timed like the compute-only loop.  Reported beside
     # `value`, which stays the sharded compute (no data-path collective).
     e2e = None
-    if dist and (world > 1 or args.gather):
+    if dist and (args.gather or (args.full and world > 1)):
         # each step's outputs and statuses in one packed buffer (one gather
         # per step), two buffers so that step k's gather overlaps step k + 1
         packs = [torch.empty(5 * lanes, dtype=torch.uint8, device="cuda") for _ in range(2)]
@@ -642,9 +685,70 @@ def main():
     if e2e is not None:
         e2e["value"] = retired / (e2e["ms_per_step"] * 1e-3 * args.steps)
         e2e["results_per_s"] = with_out / (e2e["ms_per_step"] * 1e-3 * args.steps)
+    plan = net.plan(mode=args.mode)
+    roof = roofline(args, name, plan, lanes, world, retired, launch_max, peak, peak_meas) if args.full else {}
+
+    http = None
+    if args.http and rank == 0:
+        http = http_leg(nodes, args.http, seconds=5.0)
+    sessions = None
+    if args.sessions and rank == 0:
+        with torch.cuda.stream(stream):  # the per-call reductions on the sessions' stream
+            sessions = sessions_leg(net, args.sessions, 8, stream)
+
+    if rank == 0:
+        rec = {
+            "metric": METRIC,
+            "value": value,
+            "unit": "node-instr/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": wall_max / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "int64",
+            "data": "synthetic (splitmix64 int32 /compute inputs, resident in HBM)",
+            "config": {
+                "workload": name,
+                "lanes_per_gpu": lanes,
+                "global_lanes": lanes * world,
+                "network": args.config,
+                "parallelism": f"dp{world} (contiguous lane shards, no data-path collective)",
+                "executor": plan,
+            },
+            "results_per_s": with_out / wall_max,
+            "node_instr_per_lane": retired / (lanes * world * args.steps),
+            "kernel_ms_per_step": kern_max / args.steps * 1e3,
+            "host_enqueue_us_per_step": enqueue_s / args.steps * 1e6,
+            "launch": "hip graph replay" if args.graph else "stream launches",
+        }
+        if args.full:
+            rec.update(roof)
+            cpu = None
+            if not args.no_cpu_baseline and world == 1:  # the host-core baseline is an N=1 figure
+                cpu = cpu_baseline(nodes, gen_kind, mask, args.cpu_seconds, args.refstruct_seconds)
+            rec["cpu_baseline"] = cpu
+        if e2e is not None:
+            rec["end_to_end"] = e2e
+        if host_io is not None:
+            rec["host_io"] = host_io
+        if http is not None:
+            rec["http"] = http
+        if sessions is not None:
+            rec["sessions"] = sessions
+        print(json.dumps(rec), flush=True)
+    if dist:
+        dist.destroy_process_group()
+
+
+def roofline(args, name, plan, lanes, world, retired, launch_max, peak, peak_meas):
+    """--full: the roofline fields of the result line, from the per-launch
+    time of the dominant kernel (main's second timing loop), the live VALU
+    probe and the committed PMC profile of this workload's module."""
     # ---- roofline of the dominant kernel, per launch -----------------------
     instr_per_launch = retired / world / args.steps
-    plan = net.plan(mode=args.mode)
     prof = measured_profile(name) if not args.mode and not args.gen_inputs else {}
     if prof and (abs(prof.get("retired_per_launch", 0) - instr_per_launch) > 0.01 * instr_per_launch or
                  plan_signature(prof.get("executor", "")) != plan_signature(plan)):
@@ -818,65 +922,11 @@ def main():
                 "bound": headline["bound"],
                 "note": "node-instr/s counts retired reference instructions; executed VALU lane-ops per "
                         "node-instruction from the PMC profile of this module (null: no matching profile)"}
-
-    http = None
-    if args.http and rank == 0:
-        http = http_leg(nodes, args.http, seconds=5.0)
-    sessions = None
-    if args.sessions and rank == 0:
-        with torch.cuda.stream(stream):  # the per-call reductions on the sessions' stream
-            sessions = sessions_leg(net, args.sessions, 8, stream)
-
-    if rank == 0:
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:  # the host-core baseline is an N=1 figure
-            cpu = cpu_baseline(nodes, gen_kind, mask, args.cpu_seconds, args.refstruct_seconds)
-        rec = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "node-instr/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": wall_max / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int64",
-            "data": "synthetic (splitmix64 int32 /compute inputs, resident in HBM)",
-            "config": {
-                "workload": name,
-                "lanes_per_gpu": lanes,
-                "global_lanes": lanes * world,
-                "network": args.config,
-                "parallelism": f"dp{world} (contiguous lane shards, no data-path collective)",
-                "executor": plan,
-            },
-            "results_per_s": with_out / wall_max,
-            "node_instr_per_lane": retired / (lanes * world * args.steps),
-            "kernel_ms_per_step": kern_max / args.steps * 1e3,
-            "host_enqueue_us_per_step": enqueue_s / args.steps * 1e6,
-            "launch": "hip graph replay" if args.graph else "stream launches",
-            "executed": executed,
-            "roofline": headline,
-            "roofline_issue": issue,
-            "roofline_hbm": hbm,
-            "roofline_lds": lds,
-            "cpu_baseline": cpu,
-        }
-        if stack is not None:
-            rec["stack"] = stack
-        if e2e is not None:
-            rec["end_to_end"] = e2e
-        if host_io is not None:
-            rec["host_io"] = host_io
-        if http is not None:
-            rec["http"] = http
-        if sessions is not None:
-            rec["sessions"] = sessions
-        print(json.dumps(rec), flush=True)
-    if dist:
-        dist.destroy_process_group()
+    rec = {"executed": executed, "roofline": headline, "roofline_issue": issue, "roofline_hbm": hbm,
+           "roofline_lds": lds}
+    if stack is not None:
+        rec["stack"] = stack
+    return rec
 
 
 if __name__ == "__main__":

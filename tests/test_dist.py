@@ -192,6 +192,31 @@ def test_split_covers_batch():
             assert all(parts[i][1] == parts[i + 1][0] for i in range(world - 1))
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float .npy files, every lane up to DUMP_LANES,
+    above it the same seeded sample of lanes on every run."""
+    import bench
+
+    stats = torch.arange(8, dtype=torch.int64)
+    big = bench.DUMP_LANES + 3
+    for lanes, d in ((1000, tmp_path / "a"), (big, tmp_path / "b"), (big, tmp_path / "c")):
+        out = (torch.arange(lanes, dtype=torch.int64) * 2654435761 % (1 << 32) - (1 << 31)).to(torch.int32)
+        st = (torch.arange(lanes) % 251).to(torch.uint8)
+        bench.dump_outputs(str(d), 0, out, st, stats)
+        got = {n: np.load(d / f"{n}.npy") for n in ("out", "status", "lanes", "stats")}
+        assert sorted(os.listdir(d)) == ["lanes.npy", "out.npy", "stats.npy", "status.npy"]
+        assert got["out"].dtype == got["lanes"].dtype == got["stats"].dtype == np.float64
+        assert got["status"].dtype == np.float32
+        idx = got["lanes"].astype(np.int64)
+        assert idx.size == min(lanes, bench.DUMP_LANES) and (np.diff(idx) > 0).all() and idx[-1] < lanes
+        assert np.array_equal(got["out"], out.numpy()[idx]) and np.array_equal(got["status"], st.numpy()[idx])
+        assert got["stats"].tolist() == list(range(8))
+        assert sum(a.nbytes for a in got.values()) <= 64e6
+    assert idx.size < lanes and np.array_equal(idx, np.load(tmp_path / "b" / "lanes.npy"))  # the sample is fixed
+    bench.dump_outputs(str(tmp_path / "a"), 2, out[:5], st[:5], stats)  # rank r > 0: files of its own
+    assert np.load(tmp_path / "a" / "out_rank2.npy").tolist() == out[:5].tolist()
+
+
 def test_bench_reads_only_shipped_profiles():
     """bench.py's occupancy cap reads profiles/valu_rates.jsonl on the GPU
     box; a .gpurunignore pattern that matched it would silently null the

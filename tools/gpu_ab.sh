@@ -28,7 +28,7 @@ for set in "$@"; do
   for w in $rest; do
     if [[ "$w" == *=* && ${#args[@]} -eq 0 ]]; then envs+=("$w"); else args+=("$w"); fi
   done
-  step 300 env "${envs[@]}" python bench.py --steps 10 --warmup 2 --no-cpu-baseline "${args[@]}" \
+  step 300 env "${envs[@]}" python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline "${args[@]}" \
     > "$OUT/bench_$label.log" 2>&1 || { echo "[gpu_ab] failed: $set"; tail -20 "$OUT/bench_$label.log"; exit 1; }
   grep -h '^{' "$OUT/bench_$label.log" | python3 tools/benchline.py "$label" || true
 done

@@ -3,7 +3,7 @@
 # trace domains are combined with --pmc).  Usage: bash tools/gpu_pmc.sh tag [bench args]
 set -o pipefail
 TAG=${1:-pmc}; shift
-ARGS=${@:---steps 3 --warmup 1 --no-cpu-baseline}
+ARGS=${@:---full --steps 3 --warmup 1 --no-cpu-baseline}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp

@@ -18,7 +18,7 @@ for cfg in "$@"; do
     case $pass in SQ) ctr=$SQ ;; LDS) ctr=$LDS ;; *) ctr=$pass ;; esac
     echo "[pmc] $(date +%T) $cfg $pass"; mkdir -p "$OUT/$cfg"
     timeout -s KILL 150 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d "$OUT/$cfg/$pass" -o p -- \
-      python3 bench.py --config $cfg --steps 6 --warmup 1 --no-cpu-baseline > "$OUT/$cfg/$pass.log" 2>&1 \
+      python3 bench.py --full --config $cfg --steps 6 --warmup 1 --no-cpu-baseline > "$OUT/$cfg/$pass.log" 2>&1 \
       || { echo "[pmc] failed $cfg $pass"; tail -5 "$OUT/$cfg/$pass.log"; exit 1; }
   done
 done

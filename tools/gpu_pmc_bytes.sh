@@ -9,6 +9,6 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "[pmc-bytes] $(date +%T) $c: $1"
-  timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$OUT/$c" -o p -- python3 bench.py $1 > "$OUT/$c.log" 2>&1 || { echo "[pmc-bytes] failed $c"; tail -5 "$OUT/$c.log"; exit 1; }
+  timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$OUT/$c" -o p -- python3 bench.py --full $1 > "$OUT/$c.log" 2>&1 || { echo "[pmc-bytes] failed $c"; tail -5 "$OUT/$c.log"; exit 1; }
 done
 echo "[pmc-bytes] done"

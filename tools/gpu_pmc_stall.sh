@@ -17,7 +17,7 @@ STALL2="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAIT_
 for pass in STALL STALL2; do
 echo "[pmc-stall] $(date +%T) $CFG $pass"
 timeout -s KILL 150 rocprofv3 --kernel-trace --pmc ${!pass} --output-format csv -d "$OUT/$pass" -o p -- \
-  python3 ${PMC_ARGS:-bench.py --config $CFG --steps 6 --warmup 1 --no-cpu-baseline} > "$OUT/$pass.log" 2>&1 \
+  python3 ${PMC_ARGS:-bench.py --full --config $CFG --steps 6 --warmup 1 --no-cpu-baseline} > "$OUT/$pass.log" 2>&1 \
   || { echo "[pmc-stall] failed"; tail -5 "$OUT/$pass.log"; exit 1; }
 python3 - "$OUT/$pass" <<'PY'
 import collections, csv, glob, sys

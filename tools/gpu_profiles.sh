@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 for c in "$@"; do
   echo "[gpu_profiles] $(date +%T) $c"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$c" -o "$c" \
-    -- python bench.py --config "$c" --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/prof_$c.log" 2>&1 \
+    -- python bench.py --full --config "$c" --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/prof_$c.log" 2>&1 \
     || { echo "[gpu_profiles] failed: $c"; tail -20 "$OUT/prof_$c.log"; exit 1; }
   grep -h '^{' "$OUT/prof_$c.log" > "$OUT/bench_$c.json" || true
   python3 tools/benchline.py "$c" < "$OUT/bench_$c.json" || true

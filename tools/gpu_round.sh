@@ -41,13 +41,13 @@ if [ $SMOKE = 1 ]; then
 fi
 SETS=()
 if [ $ALL = 1 ]; then
-  SETS+=("python bench.py --steps 20 --warmup 3 --cpu-seconds 10"
-         "python bench.py --config c3 --steps 20 --warmup 3 --no-cpu-baseline"
-         "python bench.py --config c4 --steps 20 --warmup 3 --no-cpu-baseline"
-         "python bench.py --config c4d256 --steps 10 --warmup 2 --no-cpu-baseline"
-         "python bench.py --config c4d1024 --steps 5 --warmup 1 --no-cpu-baseline"
-         "python bench.py --config c5 --steps 10 --warmup 2 --no-cpu-baseline"
-         "python bench.py --steps 5 --warmup 1 --no-cpu-baseline --sessions 1048576")
+  SETS+=("python bench.py --full --steps 20 --warmup 3 --cpu-seconds 10"
+         "python bench.py --full --config c3 --steps 20 --warmup 3 --no-cpu-baseline"
+         "python bench.py --full --config c4 --steps 20 --warmup 3 --no-cpu-baseline"
+         "python bench.py --full --config c4d256 --steps 10 --warmup 2 --no-cpu-baseline"
+         "python bench.py --full --config c4d1024 --steps 5 --warmup 1 --no-cpu-baseline"
+         "python bench.py --full --config c5 --steps 10 --warmup 2 --no-cpu-baseline"
+         "python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --sessions 1048576")
 fi
 SETS+=("$@")
 i=0

@@ -8,6 +8,6 @@ i=0
 for a in "$@"; do
   i=$((i+1))
   echo "[bench_set] $(date +%T) $a"
-  timeout -k 10 300 python bench.py $a > $OUT/b$i.log 2>&1 || { echo "[bench_set] failed: $a"; tail -20 $OUT/b$i.log; exit 1; }
+  timeout -k 10 300 python bench.py --full $a > $OUT/b$i.log 2>&1 || { echo "[bench_set] failed: $a"; tail -20 $OUT/b$i.log; exit 1; }
   grep -h '^{' $OUT/b$i.log | tee -a $OUT/lines.jsonl | python3 tools/benchline.py "$a" || true
 done

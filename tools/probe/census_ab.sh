@@ -11,7 +11,7 @@ for pass in 1 2; do
   for set in "$@"; do
     label=${set%%:*}
     envs=${set#*:}
-    env $envs timeout -k 10 200 python3 bench.py --config $CFG --steps 5 --warmup 1 --no-cpu-baseline \
+    env $envs timeout -k 10 200 python3 bench.py --full --config $CFG --steps 5 --warmup 1 --no-cpu-baseline \
       > "$OUT/${CFG}_${label}_$pass.log" 2>&1 || { echo "[census_ab] failed: $label"; exit 1; }
     grep -h '^{' "$OUT/${CFG}_${label}_$pass.log" | python3 -c "
 import json, sys

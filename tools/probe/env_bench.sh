@@ -8,7 +8,7 @@ for pass in 1 2; do
  for set in "$@"; do
   lab=${set%%:*}; envs=${set#*:}
   for c in $CFGS; do
-   env $envs timeout -k 10 200 python bench.py --config $c --no-cpu-baseline --steps 20 > $OUT/b.log 2>&1 || { echo "fail $lab $c"; tail -5 $OUT/b.log; exit 1; }
+   env $envs timeout -k 10 200 python bench.py --full --config $c --no-cpu-baseline --steps 20 > $OUT/b.log 2>&1 || { echo "fail $lab $c"; tail -5 $OUT/b.log; exit 1; }
    grep -h '^{' $OUT/b.log | sed "s/^/{\"label\": \"$lab\", \"r\": /; s/\$/}/" >> $OUT/ab.jsonl
   done
  done

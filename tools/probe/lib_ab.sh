@@ -14,7 +14,7 @@ for pass in 1 2; do
    echo "{\"label\": \"$v\", \"r\": $(timeout -k 10 120 python -u tools/probe/c5_decomp.py $m 4194304 20)}" >> $OUT/c5.jsonl || exit 1
   done
   for c in $CFGS; do
-   timeout -k 10 200 python bench.py --config $c --no-cpu-baseline --steps 20 > $OUT/b.log 2>&1 || { echo "fail $v $c"; tail -5 $OUT/b.log; exit 1; }
+   timeout -k 10 200 python bench.py --full --config $c --no-cpu-baseline --steps 20 > $OUT/b.log 2>&1 || { echo "fail $v $c"; tail -5 $OUT/b.log; exit 1; }
    grep -h '^{' $OUT/b.log | sed "s/^/{\"label\": \"$v\", \"r\": /; s/\$/}/" >> $OUT/ab.jsonl
   done
  done

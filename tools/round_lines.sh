@@ -12,7 +12,7 @@ bash tools/probe/bench_set.sh $TAG "--config c2" "--config c3" "--config c4" "--
   "--config t_ring16 --steps 10" || exit 1
 export TMPDIR=/tmp
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus 2 --same-device --dist-backend gloo --steps 5 --no-cpu-baseline \
+  --master-port 29533 bench.py --full --gpus 2 --same-device --dist-backend gloo --steps 5 --no-cpu-baseline \
   > gpurun_out/$TAG/two_rank.log 2>&1 || { tail -20 gpurun_out/$TAG/two_rank.log; exit 1; }
 grep -h '^{' gpurun_out/$TAG/two_rank.log >> gpurun_out/$TAG/lines.jsonl
 echo "[round_lines] done"
