@@ -291,6 +291,44 @@ int mk_session_plan(const mk_session *s, char *out, size_t out_len);
 /* /reset (master.go:126-143): every session back to the initial state. */
 int mk_session_reset(mk_session *s);
 
+/* ---- indexed forms: calls, resumes and resets on a chosen subset -----------
+ * An index list sel[0..m) names the sessions a launch acts on: uint32_t,
+ * strictly increasing, every entry < n (so m <= n).  Entry t of the launch is
+ * session sel[t]: the I/O arrays have m columns, not n -- call c of entry t
+ * takes in[c*m + t] and reports out/status/steps[c*m + t].  A session outside
+ * the list is not touched: its registers, ports, stacks, inChan / outChan,
+ * its open call and the tier that holds it stay as they were -- frozen, as
+ * every session is between calls.  Indexed and plain launches on one set are
+ * ordered against each other like the plain ones, whatever they select.
+ * m == 0 is MK_OK and launches nothing.
+ *
+ * The host forms (host arrays, synchronous) check the list and return
+ * MK_EINVAL for a bad one before anything is queued; they return MK_EBUSY
+ * when a LISTED session reported MK_ST_CALL_OPEN on a new call. */
+int mk_session_compute_indexed(mk_session *s, const uint32_t *sel, size_t m, const int64_t *in, size_t ncalls,
+                               int32_t *out, uint8_t *status, uint32_t *steps);
+/* mk_session_step on the listed sessions; in NULL: resume their open calls. */
+int mk_session_step_indexed(mk_session *s, const uint32_t *sel, size_t m, const int64_t *in, int32_t *out,
+                            uint8_t *status, uint32_t *steps);
+/* mk_session_compute_seq_device on the listed sessions.  d_sel is a device
+ * array taken ON TRUST: the caller guarantees that it is strictly increasing
+ * with every entry < n (two entries naming one session would race on its
+ * state), and keeps it valid and unchanged until the launch completes.  The
+ * only net below that contract: an entry >= n touches no session and reports
+ * out 0 / status 0. */
+int mk_session_compute_indexed_device(mk_session *s, const uint32_t *d_sel, size_t m, const int64_t *d_in,
+                                      size_t ncalls, int32_t *d_out, uint8_t *d_status, uint32_t *d_steps,
+                                      void *stream);
+/* mk_session_cancel / mk_session_reset for the listed sessions only.  A
+ * reset clears the set's MK_EDEVICE-after-a-failed-launch condition only when
+ * the list covers every session. */
+int mk_session_cancel_indexed(mk_session *s, const uint32_t *sel, size_t m);
+int mk_session_reset_indexed(mk_session *s, const uint32_t *sel, size_t m);
+/* open[t] = 1 when session sel[t] has a call open (MK_ST_BUDGET or
+ * MK_ST_REMOTE_WAIT was its last word), else 0.  sel NULL with m == n: every
+ * session.  Synchronous. */
+int mk_session_call_open(mk_session *s, const uint32_t *sel, size_t m, uint8_t *open);
+
 void mk_session_free(mk_session *s);
 
 /* Add the counters accumulated by MK_FLAG_DEFER_STATS launches on `device`

@@ -266,6 +266,130 @@ func (s *Sessions) Step(in []int) (*Result, error) {
 	return r, nil
 }
 
+// ---- indexed forms: a launch on the listed instances only -------------------
+// sel is strictly increasing with every entry < n; entry t of a result is
+// instance sel[t].  An instance outside the list is not touched: it stays
+// frozen, as every instance is between calls.
+
+func selPtr(sel []uint32) *C.uint32_t {
+	if len(sel) == 0 {
+		return nil
+	}
+	return (*C.uint32_t)(unsafe.Pointer(&sel[0]))
+}
+
+// ComputeSeqIndexed performs len(in)/len(sel) sequential /compute calls on
+// the listed instances in one launch: in[c*len(sel)+t] is call c of instance
+// sel[t] (mk_session_compute_indexed).
+func (s *Sessions) ComputeSeqIndexed(sel []uint32, in []int) (*Result, error) {
+	m := len(sel)
+	if m == 0 {
+		return &Result{}, nil
+	}
+	if len(in) == 0 || len(in)%m != 0 {
+		return nil, fmt.Errorf("mk: %d inputs for %d listed instances", len(in), m)
+	}
+	c := len(in)
+	r := &Result{Out: make([]int32, c), Status: make([]uint8, c), Steps: make([]uint32, c)}
+	in64 := make([]int64, c)
+	for i, v := range in {
+		in64[i] = int64(v)
+	}
+	rc := C.mk_session_compute_indexed(s.s, selPtr(sel), C.size_t(m), (*C.int64_t)(unsafe.Pointer(&in64[0])),
+		C.size_t(c/m), (*C.int32_t)(unsafe.Pointer(&r.Out[0])), (*C.uint8_t)(unsafe.Pointer(&r.Status[0])),
+		(*C.uint32_t)(unsafe.Pointer(&r.Steps[0])))
+	if rc != C.MK_OK {
+		return nil, fmt.Errorf("mk_session_compute_indexed: %d", int(rc))
+	}
+	return r, nil
+}
+
+// ComputeIndexed is one /compute call on each listed instance.
+func (s *Sessions) ComputeIndexed(sel []uint32, in []int) (*Result, error) {
+	if len(in) != len(sel) {
+		return nil, fmt.Errorf("mk: %d inputs for %d listed instances", len(in), len(sel))
+	}
+	return s.ComputeSeqIndexed(sel, in)
+}
+
+// StepIndexed starts a call on the listed instances (in != nil) or resumes
+// their open calls (in == nil) -- mk_session_step_indexed.
+func (s *Sessions) StepIndexed(sel []uint32, in []int) (*Result, error) {
+	m := len(sel)
+	if m == 0 {
+		return &Result{}, nil
+	}
+	r := &Result{Out: make([]int32, m), Status: make([]uint8, m), Steps: make([]uint32, m)}
+	var p *C.int64_t
+	if in != nil {
+		if len(in) != m {
+			return nil, fmt.Errorf("mk: %d inputs for %d listed instances", len(in), m)
+		}
+		in64 := make([]int64, m)
+		for i, v := range in {
+			in64[i] = int64(v)
+		}
+		p = (*C.int64_t)(unsafe.Pointer(&in64[0]))
+	}
+	rc := C.mk_session_step_indexed(s.s, selPtr(sel), C.size_t(m), p, (*C.int32_t)(unsafe.Pointer(&r.Out[0])),
+		(*C.uint8_t)(unsafe.Pointer(&r.Status[0])), (*C.uint32_t)(unsafe.Pointer(&r.Steps[0])))
+	if rc != C.MK_OK {
+		return nil, fmt.Errorf("mk_session_step_indexed: %d", int(rc))
+	}
+	return r, nil
+}
+
+// ComputeIndexedDevice queues calls on device arrays ([call][m]; dSel a
+// device uint32 array taken on trust, unchanged until the launch completes),
+// asynchronous on `stream` (nil: the set's own) --
+// mk_session_compute_indexed_device.
+func (s *Sessions) ComputeIndexedDevice(dSel unsafe.Pointer, m int, dIn unsafe.Pointer, ncalls int, dOut, dStatus,
+	dSteps, stream unsafe.Pointer) error {
+	rc := C.mk_session_compute_indexed_device(s.s, (*C.uint32_t)(dSel), C.size_t(m), (*C.int64_t)(dIn),
+		C.size_t(ncalls), (*C.int32_t)(dOut), (*C.uint8_t)(dStatus), (*C.uint32_t)(dSteps), stream)
+	if rc != C.MK_OK {
+		return fmt.Errorf("mk_session_compute_indexed_device: %d", int(rc))
+	}
+	return nil
+}
+
+// CancelIndexed abandons the listed instances' open calls (mk_session_cancel_indexed).
+func (s *Sessions) CancelIndexed(sel []uint32) error {
+	if rc := C.mk_session_cancel_indexed(s.s, selPtr(sel), C.size_t(len(sel))); rc != C.MK_OK {
+		return fmt.Errorf("mk_session_cancel_indexed: %d", int(rc))
+	}
+	return nil
+}
+
+// ResetIndexed is /reset for the listed instances only (mk_session_reset_indexed).
+func (s *Sessions) ResetIndexed(sel []uint32) error {
+	if rc := C.mk_session_reset_indexed(s.s, selPtr(sel), C.size_t(len(sel))); rc != C.MK_OK {
+		return fmt.Errorf("mk_session_reset_indexed: %d", int(rc))
+	}
+	return nil
+}
+
+// CallOpen reports which listed instances have a call open (sel nil: all n)
+// -- mk_session_call_open.
+func (s *Sessions) CallOpen(sel []uint32) ([]bool, error) {
+	m := len(sel)
+	if sel == nil {
+		m = s.n
+	}
+	open := make([]bool, m)
+	if m == 0 {
+		return open, nil
+	}
+	raw := make([]uint8, m)
+	if rc := C.mk_session_call_open(s.s, selPtr(sel), C.size_t(m), (*C.uint8_t)(unsafe.Pointer(&raw[0]))); rc != C.MK_OK {
+		return nil, fmt.Errorf("mk_session_call_open: %d", int(rc))
+	}
+	for i, v := range raw {
+		open[i] = v != 0
+	}
+	return open, nil
+}
+
 // RemoteRequest is an outstanding Program.Send / Stack.Push / Stack.Pop of a
 // parked call (mk_remote_req).
 type RemoteRequest struct {

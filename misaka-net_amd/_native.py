@@ -123,6 +123,16 @@ SIGNATURES = {
     "mk_session_compute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mk_session_compute_seq_device": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_compute_indexed": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_step_indexed": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_compute_indexed_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p]),
+    "mk_session_cancel_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mk_session_reset_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mk_session_call_open": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mk_session_reset": (C.c_int, [C.c_void_p]),
     "mk_session_cancel": (C.c_int, [C.c_void_p]),
     "mk_session_plan": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),

@@ -997,6 +997,11 @@ struct SessParams {
     // fewer per call than round 3's separate import kernel)
     uint32_t fuse_import;
     SessImport imp;
+    // selected launches (mk_session_*_indexed, tis_session<NMAX, true>):
+    // thread t of m owns session sel[t] and the I/O arrays have m columns,
+    // [ncalls][m]; the state arrays keep their stride n
+    const uint32_t *sel; // [m] strictly increasing, every entry < n
+    uint64_t m;
 };
 
 struct SessImportOut {
@@ -1043,15 +1048,20 @@ __device__ __forceinline__ void sess_import_one(const SessImport &q, const SessP
     atomicAdd(&q.sflags[1], 1u);
 }
 
-// One session instance (gid) of the interpreter kernel below; `handed`: the
+// One session instance of the interpreter kernel below; `handed`: the
 // native tier handed calls off in this launch, to be imported first.
-template <int NMAX>
-__device__ __forceinline__ void tis_session_one(const Insn *__restrict__ code, const SessParams &p, const uint64_t gid,
+// Thread t answers I/O column t of m and owns session gid: t itself in a
+// plain launch (SEL false, m == n), p.sel[t] in a selected one.  A listed
+// entry >= n is not live: it touches no state and reports out 0 / status 0.
+template <int NMAX, bool SEL>
+__device__ __forceinline__ void tis_session_one(const Insn *__restrict__ code, const SessParams &p, const uint64_t t,
                                                 int32_t *const lds, const bool handed)
 {
     const int B = kBlock;
     const int tid = threadIdx.x;
     const uint64_t n = p.n;
+    const uint64_t m = SEL ? p.m : n;
+    const uint64_t gid = SEL ? (t < m ? (uint64_t)p.sel[t] : n) : t; // the state index
     int32_t *const port = lds;                     // [nprog*4][B]
     int32_t *const sdepth = lds + p.nprog * 4 * B; // [nstack][B]
     if (handed) sess_import_one(p.imp, p, gid);
@@ -1091,7 +1101,7 @@ __device__ __forceinline__ void tis_session_one(const Insn *__restrict__ code, c
     // ncalls sequential /compute calls, the state carried in registers/LDS
     // from one to the next (a burst of requests on one instance, one launch)
     for (uint32_t call = 0; call < p.ncalls; ++call) {
-    const uint64_t ci = (uint64_t)call * n + gid;
+    const uint64_t ci = (uint64_t)call * m + t;
     // io bit 3: a call is open (it parked on peers or ran out of its slice's
     // budget); bit 2: its input is not deposited yet (held in pin).  A resume
     // continues it with its input and step count; a new call while one is
@@ -1319,6 +1329,10 @@ __device__ __forceinline__ void tis_session_one(const Insn *__restrict__ code, c
         p.out[ci] = 0;
         p.status[ci] = p.nsb[gid] == kSessDead ? (uint8_t)MK_ST_STACK_OVERFLOW : (uint8_t)0;
         if (p.steps) p.steps[ci] = 0u;
+    } else if (SEL && t < m && gid >= n) { // a listed entry that names no session
+        p.out[ci] = 0;
+        p.status[ci] = (uint8_t)0;
+        if (p.steps) p.steps[ci] = 0u;
     }
     } // calls
 
@@ -1353,7 +1367,9 @@ __device__ __forceinline__ void tis_session_one(const Insn *__restrict__ code, c
 // tier's -- the common case, each thread leaving at the flag test -- costs
 // a small grid instead of one block per 256 sessions (round 4: the per-call
 // launch pair's second half).
-template <int NMAX>
+// SEL: the selected launch, whose grid-stride loop runs over the m listed
+// sessions instead of all n.
+template <int NMAX, bool SEL>
 __global__ void __launch_bounds__(kBlock) tis_session(const Insn *__restrict__ code, SessParams p)
 {
     extern __shared__ int32_t lds[];
@@ -1365,9 +1381,10 @@ __global__ void __launch_bounds__(kBlock) tis_session(const Insn *__restrict__ c
         return; // every session is the native tier's
     }
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t end = (p.n + kBlock - 1) / kBlock * kBlock; // whole blocks: every thread takes the same trips
-    for (uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x; gid < end; gid += stride)
-        tis_session_one<NMAX>(code, p, gid, lds, handed);
+    const uint64_t cols = SEL ? p.m : p.n;
+    const uint64_t end = (cols + kBlock - 1) / kBlock * kBlock; // whole blocks: every thread takes the same trips
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < end; t += stride)
+        tis_session_one<NMAX, SEL>(code, p, t, lds, handed);
 }
 
 // mk_session_cancel: abandon every open call (io bits 2-3); the state the
@@ -1376,6 +1393,83 @@ __global__ void __launch_bounds__(kBlock) tis_session_cancel(uint32_t *io, uint6
 {
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i < n) io[i] &= ~0xCu;
+}
+
+// mk_session_cancel_indexed: the same for the m listed sessions only.
+__global__ void __launch_bounds__(kBlock) tis_session_cancel_sel(uint32_t *io, uint64_t n, const uint32_t *sel,
+                                                                 uint64_t m)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= m) return;
+    const uint64_t i = sel[t];
+    if (i < n) io[i] &= ~0xCu;
+}
+
+// mk_session_call_open: open[t] = session sel[t] (t itself with sel null) has
+// a call open (io bit 3).  Sessions the native tier holds never have one: a
+// call that stays open was handed to the interpreter, whose io word this is.
+__global__ void __launch_bounds__(kBlock) tis_session_open_sel(const uint32_t *io, uint64_t n, const uint32_t *sel,
+                                                               uint64_t m, uint8_t *open)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= m) return;
+    const uint64_t i = sel ? (uint64_t)sel[t] : t;
+    open[t] = i < n ? (uint8_t)((io[i] >> 3) & 1u) : (uint8_t)0;
+}
+
+// mk_session_reset_indexed: the m listed sessions back to the post-/reset
+// state, which is all zeroes in both state blocks (mk_session_create's
+// memsets; zero is the session schedule's first variant).  blockIdx.y 0
+// clears a session's words and counts it out of the interpreter's sessions
+// (sflags[1], so that launches skip the interpreter pass again once it holds
+// none); the rows of the three [row][session] arrays whose height follows the
+// network -- stack entries, native registers and stack slots -- are shared
+// among the grid's y.
+struct SessResetSel {
+    uint32_t *nsb, *hand_sb, *hand_steps, *hand_call, *sflags; // null without the native tier
+    int64_t *regs;
+    int32_t *slots;
+    uint32_t nregs, nslots;
+};
+
+__global__ void __launch_bounds__(kBlock) tis_session_reset_sel(SessParams p, SessResetSel q, const uint32_t *sel,
+                                                                uint64_t m)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= m) return;
+    const uint64_t i = sel[t], n = p.n;
+    if (i >= n) return;
+    const uint64_t srows = (uint64_t)p.nstack * p.stack_cap;
+    for (uint64_t r = blockIdx.y; r < srows; r += gridDim.y) p.stk[r * n + i] = 0;
+    if (q.nsb) {
+        for (uint64_t r = blockIdx.y; r < q.nregs; r += gridDim.y) q.regs[r * n + i] = 0;
+        for (uint64_t r = blockIdx.y; r < q.nslots; r += gridDim.y) q.slots[r * n + i] = 0;
+    }
+    if (blockIdx.y) return;
+    for (int k = 0; k < p.nprog; ++k) {
+        p.acc[(uint64_t)k * n + i] = 0;
+        p.bak[(uint64_t)k * n + i] = 0;
+        p.ip[(uint64_t)k * n + i] = 0;
+        p.pendv[(uint64_t)k * n + i] = 0;
+        p.xst[(uint64_t)k * n + i] = 0u;
+        p.xval[(uint64_t)k * n + i] = 0;
+    }
+    for (int k = 0; k < p.nprog * 4; ++k) p.port[(uint64_t)k * n + i] = 0;
+    for (int k = 0; k < p.nstack; ++k) p.sdepth[(uint64_t)k * n + i] = 0;
+    p.pfull[i] = 0ull;
+    p.bits[i] = 0u;
+    p.io[i] = 0u;
+    p.in_val[i] = 0;
+    p.out_val[i] = 0;
+    p.pin[i] = 0;
+    p.csteps[i] = 0u;
+    if (q.nsb) {
+        if (q.nsb[i] == kSessT1) atomicSub(&q.sflags[1], 1u);
+        q.nsb[i] = 0u;
+        q.hand_sb[i] = 0u;
+        q.hand_steps[i] = 0u;
+        q.hand_call[i] = 0u;
+    }
 }
 
 // Native sessions handed off in this launch (MK_SS_HAND: a call's budget
@@ -3327,15 +3421,19 @@ int launch_locked(mk_net *h, int d, const mk_input *in, size_t n, int32_t *d_out
 
 // ---- stateful sessions: host side -----------------------------------------
 template <int NMAX>
-void *session_kernel_ptr() { return reinterpret_cast<void *>(&tis_session<NMAX>); }
-
-void *pick_session_kernel(int nprog)
+void *session_kernel_ptr(bool sel)
 {
-    if (nprog <= 1) return session_kernel_ptr<1>();
-    if (nprog <= 2) return session_kernel_ptr<2>();
-    if (nprog <= 4) return session_kernel_ptr<4>();
-    if (nprog <= 8) return session_kernel_ptr<8>();
-    return session_kernel_ptr<16>();
+    return sel ? reinterpret_cast<void *>(&tis_session<NMAX, true>)
+               : reinterpret_cast<void *>(&tis_session<NMAX, false>);
+}
+
+void *pick_session_kernel(int nprog, bool sel = false)
+{
+    if (nprog <= 1) return session_kernel_ptr<1>(sel);
+    if (nprog <= 2) return session_kernel_ptr<2>(sel);
+    if (nprog <= 4) return session_kernel_ptr<4>(sel);
+    if (nprog <= 8) return session_kernel_ptr<8>(sel);
+    return session_kernel_ptr<16>(sel);
 }
 
 } // namespace
@@ -3364,6 +3462,8 @@ struct mk_session {
     std::string plan; // mk_session_plan
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
+    hipFunction_t fn_sel = nullptr; // the module's selected entry (kJitSessSelKernel)
+    uint32_t nregs = 0, nslots = 0; // rows of regs and slots (mk_session_reset_indexed)
     std::vector<char> code; // the module's code object: HIP may read the image after hipModuleLoadData
     std::string rtc_from;   // its compiler (load_module / release_module)
     void *d_native = nullptr; // every native array, one allocation
@@ -3415,6 +3515,12 @@ struct SessK {
     uint32_t *sflags;
     uint32_t epoch;
 };
+// ... and of its selected entry (SessKSel)
+struct SessKSel {
+    SessK k;
+    const uint32_t *sel;
+    uint64_t m;
+};
 
 // *queued (when given) is set once a kernel has been queued on `stream`, so
 // that a caller whose launch fails part way still orders later work after it.
@@ -3422,13 +3528,17 @@ struct SessK {
 // completion event (hipExtModuleLaunchKernel / hipExtLaunchKernel stop
 // event), instead of by a separate hipEventRecord after it: that marker cost
 // ~3 us of stream time per call (round 6, profiles/r08_sessions_ab.txt).
+// With d_sel the launch is a selected one: m threads, thread t on session
+// d_sel[t], the I/O arrays [ncalls][m]; the grids cover m, not n.
 int session_launch(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *d_status, uint32_t *d_steps,
                    hipStream_t stream, uint32_t ncalls = 1, bool resume = false, bool *queued = nullptr,
-                   hipEvent_t done = nullptr)
+                   hipEvent_t done = nullptr, const uint32_t *d_sel = nullptr, uint64_t m = 0)
 {
     if (s->broken) return MK_EDEVICE;
-    if (s->n == 0 || ncalls == 0) return MK_OK;
+    if (s->n == 0 || ncalls == 0 || (d_sel && m == 0)) return MK_OK;
     SessParams p = s->p;
+    p.sel = d_sel;
+    p.m = m;
     p.ncalls = ncalls;
     p.resume = resume ? 1u : 0u;
     p.in = d_in;
@@ -3437,20 +3547,23 @@ int session_launch(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *
     p.steps = d_steps;
     const Insn *code = s->h->dev[s->device].d_code;
     const size_t lds = (size_t)(s->nprog * 4 + s->nstack) * kBlock * 4;
-    const uint64_t blocks = (s->n + kBlock - 1) / kBlock;
+    const uint64_t blocks = ((d_sel ? m : (uint64_t)s->n) + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffull) return MK_ELIMIT;
+    // hipExtModuleLaunchKernel takes the grid in threads, 32 bits
+    if (d_sel && blocks * kBlock > 0xffffffffull) return MK_ELIMIT;
     const uint64_t iblocks = blocks < kSessGridCap ? blocks : kSessGridCap; // the interpreter's grid-stride grid
     if (s->native && !resume) {
         if (++s->epoch == 0) s->epoch = 1; // sflags[0] starts at 0: "no hand-off yet"
         // 1. the native kernel: every session it holds, every call of the burst
         SessK k{s->n, ncalls, p.budget, d_in, d_out, d_status, d_steps, s->nsb, s->regs, s->slots,
                 s->hand_sb, s->hand_steps, s->hand_call, s->sflags, s->epoch};
-        void *kargs[] = {(void *)&k};
+        SessKSel ks{k, d_sel, m};
+        void *kargs[] = {d_sel ? (void *)&ks : (void *)&k};
         // the native kernel is the launch's last when the interpreter pass is
         // skipped (below: no call can reach the budget)
         const bool last = s->call_steps < (uint64_t)p.budget;
-        if (hipExtModuleLaunchKernel(s->fn, (uint32_t)(blocks * kBlock), 1, 1, kBlock, 1, 1, 0, stream, kargs, nullptr,
-                                     nullptr, last ? done : nullptr, 0) != hipSuccess)
+        if (hipExtModuleLaunchKernel(d_sel ? s->fn_sel : s->fn, (uint32_t)(blocks * kBlock), 1, 1, kBlock, 1, 1, 0,
+                                     stream, kargs, nullptr, nullptr, last ? done : nullptr, 0) != hipSuccess)
             return MK_EDEVICE;
         if (queued) *queued = true;
         // 2. calls it handed off become interpreter sessions: imported by
@@ -3464,8 +3577,8 @@ int session_launch(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *
     }
     // 3. the interpreter: its sessions (all of them without the native tier)
     void *args[] = {(void *)&code, (void *)&p};
-    if (hipExtLaunchKernel(pick_session_kernel(s->nprog), dim3((unsigned)iblocks), dim3(kBlock), args, lds, stream,
-                           nullptr, done, 0) != hipSuccess) {
+    if (hipExtLaunchKernel(pick_session_kernel(s->nprog, d_sel != nullptr), dim3((unsigned)iblocks), dim3(kBlock), args,
+                           lds, stream, nullptr, done, 0) != hipSuccess) {
         if (s->native && !resume) s->broken = true;
         return MK_EDEVICE;
     }
@@ -3503,7 +3616,8 @@ int session_native(mk_session *s)
     DeviceGuard g(s->device);
     s->rtc_from = from;
     if (load_module(s->device, code, from, &s->mod) != hipSuccess ||
-        hipModuleGetFunction(&s->fn, s->mod, kJitSessKernel) != hipSuccess)
+        hipModuleGetFunction(&s->fn, s->mod, kJitSessKernel) != hipSuccess ||
+        hipModuleGetFunction(&s->fn_sel, s->mod, kJitSessSelKernel) != hipSuccess)
         return MK_EDEVICE;
     std::vector<SessMapHdr> hdr;
     std::vector<SessSrcDev> rec;
@@ -3530,6 +3644,8 @@ int session_native(mk_session *s)
     s->hdr = (SessMapHdr *)take(7);
     s->rec = (SessSrcDev *)take(8);
     s->dyn_base = (int64_t *)take(9);
+    s->nregs = P.nregs;
+    s->nslots = std::max<uint32_t>(P.nslots, 1);
     // the maps never change: copied once (reset clears only the lane state)
     if ((!hdr.empty() && hipMemcpy(s->hdr, hdr.data(), hdr.size() * sizeof(SessMapHdr), hipMemcpyHostToDevice) !=
                              hipSuccess) ||
@@ -4122,6 +4238,230 @@ int mk_session_cancel(mk_session *s)
                         args, 0, s->stream) != hipSuccess)
         return MK_EDEVICE;
     return hipStreamSynchronize(s->stream) == hipSuccess ? MK_OK : MK_EDEVICE;
+}
+
+// ---- indexed forms: a launch on the m listed sessions only ------------------
+extern "C++" {
+namespace mk {
+namespace {
+// The host forms' check of an index list: at most n entries, strictly
+// increasing (so no two threads of a launch share a session), every one < n.
+bool sel_valid(const mk_session *s, const uint32_t *sel, size_t m)
+{
+    if (m > s->n || (m && !sel)) return false;
+    for (size_t t = 0; t < m; t++)
+        if (sel[t] >= s->n || (t && sel[t] <= sel[t - 1])) return false;
+    return true;
+}
+
+// The host-API staging (d_stage and its pinned mirror) with room for `need`
+// bytes.  Caller holds s->mu.
+int session_stage(mk_session *s, size_t need)
+{
+    if (need <= s->stage_bytes) return MK_OK;
+    (void)hipFree(s->d_stage);
+    (void)hipHostFree(s->h_stage);
+    s->d_stage = s->h_stage = nullptr;
+    s->stage_bytes = 0;
+    if (hipMalloc(&s->d_stage, need) != hipSuccess) return MK_ENOMEM;
+    if (hipHostMalloc(&s->h_stage, need, hipHostMallocDefault) != hipSuccess) return MK_ENOMEM;
+    s->stage_bytes = need;
+    return MK_OK;
+}
+
+size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// session_host_calls for an index list: the staging holds in, out, steps,
+// status ([ncalls][m] each) and then sel.
+int session_host_calls_sel(mk_session *s, const uint32_t *sel, size_t m, const int64_t *in, size_t ncalls,
+                           int32_t *out, uint8_t *status, uint32_t *steps, bool resume)
+{
+    if (ncalls > 0xffffffffull) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!sel_valid(s, sel, m)) return MK_EINVAL;
+    if (m == 0 || ncalls == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    if (int rc = session_wait_last(s, s->stream)) return rc;
+    const size_t c = m * ncalls;
+    const size_t a8 = al256(c * 8), a4 = al256(c * 4), a1 = al256(c), o_sel = a8 + a4 + a4 + a1;
+    if (int rc = session_stage(s, o_sel + al256(m * 4))) return rc;
+    char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
+    int64_t *din = (int64_t *)b;
+    int32_t *dout = (int32_t *)(b + a8);
+    uint32_t *dsteps = (uint32_t *)(b + a8 + a4);
+    uint8_t *dst = (uint8_t *)(b + a8 + a4 + a4);
+    uint32_t *dsel = (uint32_t *)(b + o_sel);
+    if (in) memcpy(hb, in, c * 8);
+    else memset(hb, 0, c * 8); // resume: the kernel ignores the inputs
+    memcpy(hb + o_sel, sel, m * 4);
+    if (hipMemcpyAsync(din, hb, c * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipMemcpyAsync(dsel, hb + o_sel, m * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    int rc = session_launch(s, din, dout, dst, steps ? dsteps : nullptr, s->stream, (uint32_t)ncalls, resume, nullptr,
+                            nullptr, dsel, m);
+    if (rc) return rc;
+    if (hipMemcpyAsync(hb + a8, dout, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipMemcpyAsync(hb + a8 + a4 + a4, dst, c, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    if (steps && hipMemcpyAsync(hb + a8 + a4, dsteps, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
+    memcpy(out, hb + a8, c * 4);
+    memcpy(status, hb + a8 + a4 + a4, c);
+    if (steps) memcpy(steps, hb + a8 + a4, c * 4);
+    // a listed session that had a call open when this launch began did nothing
+    if (!resume)
+        for (size_t t = 0; t < m; t++)
+            if (status[t] == MK_ST_CALL_OPEN) return MK_EBUSY;
+    return MK_OK;
+}
+
+// The list on the device, in the staging (at its start), for the small
+// indexed kernels; *d_sel is null for a null list.  Caller holds s->mu and
+// has ordered s->stream after the set's last launch.
+int session_stage_sel(mk_session *s, const uint32_t *sel, size_t m, size_t extra, uint32_t **d_sel)
+{
+    const size_t a = sel ? al256(m * 4) : 0;
+    if (int rc = session_stage(s, a + extra)) return rc;
+    *d_sel = nullptr;
+    if (!sel) return MK_OK;
+    memcpy(s->h_stage, sel, m * 4);
+    if (hipMemcpyAsync(s->d_stage, s->h_stage, m * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    *d_sel = (uint32_t *)s->d_stage;
+    return MK_OK;
+}
+
+// Grid of the small indexed kernels: one thread per listed session.
+bool sel_grid(size_t m, unsigned *blocks)
+{
+    const uint64_t b = ((uint64_t)m + kBlock - 1) / kBlock;
+    if (b * kBlock > 0xffffffffull) return false;
+    *blocks = (unsigned)b;
+    return true;
+}
+} // namespace
+} // namespace mk
+}
+
+int mk_session_compute_indexed(mk_session *s, const uint32_t *sel, size_t m, const int64_t *in, size_t ncalls,
+                               int32_t *out, uint8_t *status, uint32_t *steps)
+{
+    if (!s || (m && ncalls && (!in || !out || !status))) return MK_EINVAL;
+    return mk::session_host_calls_sel(s, sel, m, in, ncalls, out, status, steps, false);
+}
+
+int mk_session_step_indexed(mk_session *s, const uint32_t *sel, size_t m, const int64_t *in, int32_t *out,
+                            uint8_t *status, uint32_t *steps)
+{
+    if (!s || (m && (!out || !status))) return MK_EINVAL;
+    return mk::session_host_calls_sel(s, sel, m, in, 1, out, status, steps, in == nullptr);
+}
+
+int mk_session_compute_indexed_device(mk_session *s, const uint32_t *d_sel, size_t m, const int64_t *d_in,
+                                      size_t ncalls, int32_t *d_out, uint8_t *d_status, uint32_t *d_steps,
+                                      void *stream)
+{
+    if (!s || (m && ncalls && (!d_sel || !d_in || !d_out || !d_status))) return MK_EINVAL;
+    if (ncalls > 0xffffffffull || m > s->n) return MK_EINVAL;
+    if (m == 0 || ncalls == 0) return MK_OK;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::DeviceGuard g(s->device);
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    // ordered against every other launch of the set, whatever it selected
+    // (mk_session_compute_seq_device)
+    if (int rc = mk::session_wait_last(s, st)) return rc;
+    bool queued = false;
+    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
+    int rc = mk::session_launch(s, d_in, d_out, d_status, d_steps, st, (uint32_t)ncalls, false, &queued, s->order,
+                                d_sel, m);
+    if (rc) {
+        if (queued) (void)mk::session_mark(s, st);
+        return rc;
+    }
+    s->last = st;
+    return MK_OK;
+}
+
+int mk_session_cancel_indexed(mk_session *s, const uint32_t *sel, size_t m)
+{
+    if (!s) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!mk::sel_valid(s, sel, m)) return MK_EINVAL;
+    if (m == 0) return MK_OK;
+    unsigned blocks;
+    if (!mk::sel_grid(m, &blocks)) return MK_ELIMIT;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    uint32_t *d_sel;
+    if (int rc = mk::session_stage_sel(s, sel, m, 0, &d_sel)) return rc;
+    uint32_t *io = s->p.io;
+    uint64_t n = s->n, mm = m;
+    void *args[] = {(void *)&io, (void *)&n, (void *)&d_sel, (void *)&mm};
+    if (hipLaunchKernel(reinterpret_cast<void *>(&mk::tis_session_cancel_sel), dim3(blocks), dim3(mk::kBlock), args, 0,
+                        s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    return hipStreamSynchronize(s->stream) == hipSuccess ? MK_OK : MK_EDEVICE;
+}
+
+int mk_session_reset_indexed(mk_session *s, const uint32_t *sel, size_t m)
+{
+    if (!s) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!mk::sel_valid(s, sel, m)) return MK_EINVAL;
+    if (m == 0) return MK_OK;
+    unsigned blocks;
+    if (!mk::sel_grid(m, &blocks)) return MK_ELIMIT;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    uint32_t *d_sel;
+    if (int rc = mk::session_stage_sel(s, sel, m, 0, &d_sel)) return rc;
+    mk::SessParams p = s->p;
+    mk::SessResetSel q{};
+    if (s->native) q = mk::SessResetSel{s->nsb, s->hand_sb, s->hand_steps, s->hand_call, s->sflags, s->regs, s->slots,
+                                        s->nregs, s->nslots};
+    // the grid's y shares the rows of the tall arrays (stack entries, registers, slots)
+    const uint64_t rows =
+        std::max<uint64_t>({(uint64_t)s->nstack * s->cap, (uint64_t)s->nregs, (uint64_t)s->nslots, (uint64_t)1});
+    uint64_t mm = m;
+    void *args[] = {(void *)&p, (void *)&q, (void *)&d_sel, (void *)&mm};
+    if (hipLaunchKernel(reinterpret_cast<void *>(&mk::tis_session_reset_sel),
+                        dim3(blocks, (unsigned)std::min<uint64_t>(rows, 64)), dim3(mk::kBlock), args, 0,
+                        s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
+    // A broken set (mk_session's `broken`) has sessions left handed off by a
+    // launch that failed part way, and the host does not know which: only a
+    // list of all n sessions is sure to have cleared every one of them.
+    if (m == s->n) s->broken = false;
+    return MK_OK;
+}
+
+int mk_session_call_open(mk_session *s, const uint32_t *sel, size_t m, uint8_t *open)
+{
+    if (!s || (m && !open)) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (sel ? !mk::sel_valid(s, sel, m) : m != s->n) return MK_EINVAL; // a null list: every session, m == n
+    if (m == 0) return MK_OK;
+    unsigned blocks;
+    if (!mk::sel_grid(m, &blocks)) return MK_ELIMIT;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    uint32_t *d_sel;
+    if (int rc = mk::session_stage_sel(s, sel, m, mk::al256(m), &d_sel)) return rc;
+    const size_t o_open = sel ? mk::al256(m * 4) : 0;
+    uint8_t *d_open = (uint8_t *)s->d_stage + o_open;
+    const uint32_t *io = s->p.io;
+    uint64_t n = s->n, mm = m;
+    void *args[] = {(void *)&io, (void *)&n, (void *)&d_sel, (void *)&mm, (void *)&d_open};
+    if (hipLaunchKernel(reinterpret_cast<void *>(&mk::tis_session_open_sel), dim3(blocks), dim3(mk::kBlock), args, 0,
+                        s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    if (hipMemcpyAsync((char *)s->h_stage + o_open, d_open, m, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipStreamSynchronize(s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    memcpy(open, (char *)s->h_stage + o_open, m);
+    return MK_OK;
 }
 
 int mk_session_plan(const mk_session *s, char *out, size_t out_len)

@@ -2930,7 +2930,7 @@ std::string module_prelude(JitShape shape, const JitLimits &lim, uint32_t pool, 
 // stops at that superblock's entry, records it, and the interpreter
 // (mk_exec.hip tis_session, which imports it first) finishes that call and the
 // rest of the burst.  Sessions the interpreter holds (MK_SS_T1) are skipped.
-const char *const kSessionKernel = R"(
+const char *const kSessionParams = R"(
 struct SessK {
     uint64_t n;
     uint32_t ncalls, budget;
@@ -2947,9 +2947,25 @@ struct SessK {
     uint32_t *sflags;    // [0]: this launch's epoch once a lane handed off (mk_exec.hip SessParams)
     uint32_t epoch;
 };
-extern "C" __global__ void __launch_bounds__(256) mk_sess_exec(SessK p)
+// The selected launch (mk_session_*_indexed): m threads, thread t on session
+// sel[t] (strictly increasing, so no two threads share a session).
+struct SessKSel {
+    SessK k;
+    const uint32_t *sel; // [m]
+    uint64_t m;
+};
+)";
+
+// The kernel's text, emitted once per entry (session_kernel below fills the
+// $ places): thread t of a launch answers I/O column t of the launch's
+// columns and owns session gid -- t itself of n columns in the plain entry,
+// sel[t] of m in the selected one.  State is indexed by gid (stride n), I/O
+// by call * columns + t.  The plain entry's text is what it was before the
+// selected one existed, so that its code is too.
+const char *const kSessionKernel = R"(
+extern "C" __global__ void __launch_bounds__(256) $ENTRY
 {
-    const uint64_t gid = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+$INDEX
     const bool live = gid < p.n;
     uint32_t sbv = live ? p.sb[gid] : MK_SS_DEAD;
     const bool native = sbv < MK_SS_DEAD;
@@ -2957,7 +2973,7 @@ extern "C" __global__ void __launch_bounds__(256) mk_sess_exec(SessK p)
     mk_sess_load(L, p.regs, gid, p.n, native);
     int32_t *slots = p.slots ? p.slots + gid : (int32_t *)0;
     for (uint32_t call = 0; call < p.ncalls; ++call) {
-        const uint64_t ci = (uint64_t)call * p.n + gid;
+        const uint64_t ci = (uint64_t)call * $COLS + $COL;
         const bool run = sbv < MK_SS_DEAD;
         L.sb = run ? sbv : MK_SB_IDLE;
         L.steps = 0u;
@@ -2990,6 +3006,7 @@ extern "C" __global__ void __launch_bounds__(256) mk_sess_exec(SessK p)
             const uint32_t us = MK_SCALAR(u); // the switch value, out of GVN's reach (MK_JIT_UNIFORM_SW)
             if (L.sb == u) mk_run(us, L, p.budget, slots, p.n, MK_POLICY, smax);
         }
+$NOSESSION
         if (!live || sbv == MK_SS_T1 || sbv == MK_SS_HAND) continue; // the interpreter answers these
         if (run && L.st == MK_SS_HANDOFF) {
             p.hand_sb[gid] = L.next / 2u;
@@ -3010,6 +3027,32 @@ extern "C" __global__ void __launch_bounds__(256) mk_sess_exec(SessK p)
     }
 }
 )";
+
+std::string session_kernel(bool sel)
+{
+    // an entry of the list that is >= n names no session: not live, it loads
+    // and stores no state and reports out 0 / status 0
+    const std::pair<const char *, const char *> fill[] = {
+        {"$ENTRY", sel ? "mk_sess_exec_sel(SessKSel q)" : "mk_sess_exec(SessK p)"},
+        {"$INDEX", sel ? "    const SessK &p = q.k;\n"
+                         "    const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;\n"
+                         "    const uint64_t gid = t < q.m ? (uint64_t)q.sel[t] : p.n;"
+                       : "    const uint64_t gid = (uint64_t)blockIdx.x * 256u + threadIdx.x;"},
+        {"$COLS", sel ? "q.m" : "p.n"}, // before $COL, its prefix
+        {"$COL", sel ? "t" : "gid"},
+        {"$NOSESSION", sel ? "        if (t < q.m && !live) {\n"
+                             "            p.out[ci] = 0;\n"
+                             "            p.status[ci] = (uint8_t)0;\n"
+                             "            if (p.steps) p.steps[ci] = 0u;\n"
+                             "        }"
+                           : ""},
+    };
+    std::string k = kSessionKernel;
+    for (const auto &f : fill)
+        for (size_t at = k.find(f.first); at != std::string::npos; at = k.find(f.first, at))
+            k.replace(at, strlen(f.first), f.second);
+    return k;
+}
 } // namespace
 
 std::string jit_module_source(const std::string &lane_src, JitShape shape, bool heavy, const JitLimits &lim,
@@ -3041,7 +3084,8 @@ bool jit_session_source(const SchedProgram &p, const JitLimits &lim, std::string
     if (!analyze(p, lim, g, why)) return false;
     Emitter e;
     emit_machine_lane(p, g, e);
-    src = module_prelude(JIT_MACHINE, lim, 0, e.s.find("MK_SAT") != std::string::npos) + e.s + kSessionKernel;
+    src = module_prelude(JIT_MACHINE, lim, 0, e.s.find("MK_SAT") != std::string::npos) + e.s + kSessionParams +
+          session_kernel(false) + session_kernel(true);
     return true;
 }
 

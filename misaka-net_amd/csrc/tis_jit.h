@@ -242,6 +242,8 @@ constexpr uint32_t kJitWaveBlockedSlots = 1u << 22;
 // as a machine-shape lane plus the kernel kJitSessKernel, one thread per
 // session, state in HBM; handed-off calls go to the interpreter.
 constexpr const char *kJitSessKernel = "mk_sess_exec";
+// its selected form in the same module: thread t on session sel[t]
+constexpr const char *kJitSessSelKernel = "mk_sess_exec_sel";
 bool jit_session_source(const SchedProgram &p, const JitLimits &lim, std::string &src, std::string &why);
 // Longest call of a session schedule in retired node-instructions
 // (UINT64_MAX: unbounded, a call can loop); see tis_jit.cpp.

@@ -309,22 +309,65 @@ class SessionSet:
         self._h, self._net, self.n, self.device = h, net, n, device
         _LIVE.add(self)
 
-    def compute(self, values, *, steps=True, busy_ok=False) -> BatchResult:
+    def _index(self, index) -> np.ndarray:
+        """An index list as the C ABI takes it (uint32, strictly increasing,
+        every entry < n); ValueError names the first offending position."""
+        a = np.asarray(index)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError(f"index must hold integers, got dtype {a.dtype}")
+        a = a.reshape(-1).astype(np.int64) if a.size else np.zeros(0, np.int64)
+        if a.size > self.n:
+            raise ValueError(f"index position {self.n}: more than the set's {self.n} instances listed")
+        bad = (a < 0) | (a >= self.n)
+        bad[1:] |= a[1:] <= a[:-1]
+        if bad.any():
+            t = int(np.argmax(bad))
+            why = "is not an instance" if not 0 <= a[t] < self.n else f"does not exceed position {t - 1}'s {a[t - 1]}"
+            raise ValueError(f"index position {t}: {a[t]} {why} (n = {self.n}; strictly increasing)")
+        return np.ascontiguousarray(a.astype(np.uint32))
+
+    def compute(self, values, *, steps=True, busy_ok=False, index=None) -> BatchResult:
         """One /compute call per instance: ``values[i]`` goes to instance i.
 
         A call whose budget slice runs out stays open (status MK_ST_BUDGET):
         :meth:`resume` continues it, :meth:`cancel` abandons it.  While one is
         open a new call on that instance does nothing (MK_ST_CALL_OPEN) and
-        this raises MkError(MK_EBUSY) unless ``busy_ok``."""
+        this raises MkError(MK_EBUSY) unless ``busy_ok``.
+
+        With ``index`` (strictly increasing instance numbers) only the listed
+        instances take a call: ``values[t]`` goes to instance ``index[t]``,
+        results have ``len(index)`` columns, and every other instance stays
+        exactly as it was."""
         v = np.ascontiguousarray(np.asarray(values, dtype=np.int64))
+        if index is not None:
+            sel = self._index(index)
+            if v.size != sel.size:
+                raise ValueError(f"expected {sel.size} values, got {v.size}")
+            return self._step_indexed(sel, v, steps, busy_ok)
         if v.size != self.n:
             raise ValueError(f"expected {self.n} values, got {v.size}")
         return self._step(v.ctypes.data_as(C.c_void_p), steps, busy_ok, "mk_session_compute")
 
-    def resume(self, *, steps=True) -> BatchResult:
+    def resume(self, *, steps=True, index=None) -> BatchResult:
         """One more budget slice of every instance's open call (instances
-        without one report status 0) -- mk_session_step(in = NULL)."""
+        without one report status 0) -- mk_session_step(in = NULL); with
+        ``index``, of the listed instances' open calls only."""
+        if index is not None:
+            return self._step_indexed(self._index(index), None, steps, False)
         return self._step(None, steps, False, "mk_session_step")
+
+    def _step_indexed(self, sel, v, steps, busy_ok) -> BatchResult:
+        m = sel.size
+        out = np.zeros(m, np.int32)
+        st = np.zeros(m, np.uint8)
+        sp = np.zeros(m, np.uint32) if steps else None
+        rc = N.lib().mk_session_step_indexed(
+            self._h, sel.ctypes.data_as(C.c_void_p), m, v.ctypes.data_as(C.c_void_p) if v is not None else None,
+            out.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p),
+            sp.ctypes.data_as(C.c_void_p) if sp is not None else None)
+        if not (busy_ok and rc == N.MK_EBUSY):
+            N.check(rc, "mk_session_step_indexed")
+        return BatchResult(out, st, sp)
 
     def _step(self, vp, steps, busy_ok, what) -> BatchResult:
         out = np.zeros(self.n, np.int32)
@@ -342,11 +385,27 @@ class SessionSet:
         N.check(N.lib().mk_session_plan(self._h, buf, len(buf)), "mk_session_plan")
         return buf.value.decode()
 
-    def cancel(self):
-        """Abandon every instance's open call (mk_session_cancel)."""
+    def cancel(self, *, index=None):
+        """Abandon every instance's open call (mk_session_cancel); with
+        ``index``, the listed instances' only."""
+        if index is not None:
+            sel = self._index(index)
+            N.check(N.lib().mk_session_cancel_indexed(self._h, sel.ctypes.data_as(C.c_void_p), sel.size),
+                    "mk_session_cancel_indexed")
+            return
         N.check(N.lib().mk_session_cancel(self._h), "mk_session_cancel")
 
-    def compute_seq(self, values, *, steps=True, busy_ok=False) -> BatchResult:
+    def call_open(self, index=None) -> np.ndarray:
+        """Which instances have a call open (uint8, 1 = open): all ``n``, or
+        the listed ones in the order of ``index`` (mk_session_call_open)."""
+        sel = self._index(index) if index is not None else None
+        m = self.n if sel is None else sel.size
+        op = np.zeros(m, np.uint8)
+        N.check(N.lib().mk_session_call_open(self._h, sel.ctypes.data_as(C.c_void_p) if sel is not None else None, m,
+                                             op.ctypes.data_as(C.c_void_p)), "mk_session_call_open")
+        return op
+
+    def compute_seq(self, values, *, steps=True, busy_ok=False, index=None) -> BatchResult:
         """Sequential /compute calls in one launch: ``values`` has shape
         (ncalls, n) -- row c is call c on every instance -- or, for n == 1,
         a flat list of the calls.  Results have the shape of ``values``.  A
@@ -354,6 +413,22 @@ class SessionSet:
         of the burst report MK_ST_CALL_OPEN without running."""
         v = np.ascontiguousarray(np.asarray(values, dtype=np.int64))
         shape = v.shape
+        if index is not None:
+            # values and results (ncalls, len(index)): column t is instance index[t]
+            sel = self._index(index)
+            if v.ndim != 2 or v.shape[1] != sel.size:
+                raise ValueError(f"expected (ncalls, {sel.size}) values, got {shape}")
+            out = np.zeros(shape, np.int32)
+            st = np.zeros(shape, np.uint8)
+            sp = np.zeros(shape, np.uint32) if steps else None
+            if v.size:
+                rc = N.lib().mk_session_compute_indexed(
+                    self._h, sel.ctypes.data_as(C.c_void_p), sel.size, v.ctypes.data_as(C.c_void_p), shape[0],
+                    out.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p),
+                    sp.ctypes.data_as(C.c_void_p) if sp is not None else None)
+                if not (busy_ok and rc == N.MK_EBUSY):
+                    N.check(rc, "mk_session_compute_indexed")
+            return BatchResult(out, st, sp)
         if v.ndim == 1 and self.n == 1:
             v = v.reshape(-1, 1)
         if v.ndim != 2 or v.shape[1] != self.n:
@@ -370,18 +445,46 @@ class SessionSet:
                 N.check(rc, "mk_session_compute_seq")
         return BatchResult(out.reshape(shape), st.reshape(shape), sp.reshape(shape) if sp is not None else None)
 
-    def compute_device(self, in_ptr, out_ptr, status_ptr, steps_ptr=None, *, stream=None):
+    def compute_device(self, in_ptr, out_ptr, status_ptr, steps_ptr=None, *, stream=None, index_ptr=None, m=None):
+        """One call on device arrays, asynchronous on ``stream``.  With
+        ``index_ptr`` (a device uint32 array of ``m`` strictly increasing
+        instance numbers, taken on trust and to be kept unchanged until the
+        launch completes) the arrays have ``m`` columns and only the listed
+        instances take the call (mk_session_compute_indexed_device)."""
+        if index_ptr is not None:
+            return self.compute_seq_device(in_ptr, 1, out_ptr, status_ptr, steps_ptr, stream=stream,
+                                           index_ptr=index_ptr, m=m)
+        if m is not None:
+            raise ValueError("m goes with index_ptr")
         N.check(N.lib().mk_session_compute_device(self._h, in_ptr, out_ptr, status_ptr, steps_ptr, stream),
                 "mk_session_compute_device")
 
-    def compute_seq_device(self, in_ptr, ncalls, out_ptr, status_ptr, steps_ptr=None, *, stream=None):
+    def compute_seq_device(self, in_ptr, ncalls, out_ptr, status_ptr, steps_ptr=None, *, stream=None, index_ptr=None,
+                           m=None):
         """A burst of `ncalls` sequential calls per instance in one launch on
-        device arrays laid out [call][instance] (mk_session_compute_seq_device)."""
+        device arrays laid out [call][instance] (mk_session_compute_seq_device);
+        with ``index_ptr`` and ``m`` as in :meth:`compute_device`, laid out
+        [call][m]."""
+        if (index_ptr is None) != (m is None):
+            raise ValueError("index_ptr and m go together")
+        if index_ptr is not None:
+            if not 0 <= m <= self.n:
+                raise ValueError(f"m = {m} outside [0, {self.n}]")
+            N.check(N.lib().mk_session_compute_indexed_device(self._h, index_ptr, m, in_ptr, ncalls, out_ptr,
+                                                              status_ptr, steps_ptr, stream),
+                    "mk_session_compute_indexed_device")
+            return
         N.check(N.lib().mk_session_compute_seq_device(self._h, in_ptr, ncalls, out_ptr, status_ptr, steps_ptr, stream),
                 "mk_session_compute_seq_device")
 
-    def reset(self):
-        """/reset (master.go:126-143): every instance back to its initial state."""
+    def reset(self, *, index=None):
+        """/reset (master.go:126-143): every instance back to its initial
+        state; with ``index``, the listed instances only."""
+        if index is not None:
+            sel = self._index(index)
+            N.check(N.lib().mk_session_reset_indexed(self._h, sel.ctypes.data_as(C.c_void_p), sel.size),
+                    "mk_session_reset_indexed")
+            return
         N.check(N.lib().mk_session_reset(self._h), "mk_session_reset")
 
     def close(self):
