@@ -1222,13 +1222,23 @@ void emit_self_loop(const OpWriter &w, const Graph &g, uint32_t v, size_t gpc, s
     const DOp *brx = g.D[gpc + 1].op == U_BRX ? &g.D[gpc + 1] : nullptr;
     // induction register: written once per iteration, by r += imm (no
     // truncation).  Loops with an OVF / BRX exit have one too since round 6
-    // (a dynamic PUSH loop's depth register): the exit drops the lane's flag
-    // before the bump, so the bumps count exactly the iterations completed,
-    // as the per-lane counter did; the register then needs no select and
-    // runs in 32 bits in the narrow phase (t2_dyn_depth 130 -> ? us).
+    // (a dynamic PUSH loop's depth register), under an ordering rule: the
+    // bump must come after the body's last OVF / BRX.  An exit drops the
+    // lane's flag where it stands, and the unguarded phases predicate the
+    // bump on that flag, so only a bump behind every exit counts exactly the
+    // iterations completed, as the per-lane counter does; a bump ahead of an
+    // exit (a loop that counts before it pushes) is taken by the lane that
+    // then leaves, and its steps would come out one iteration too high.
+    // Such a register is no induction register: the next candidate is
+    // tried, and without one the per-lane counter k counts.  With one the
+    // register needs no select and runs in 32 bits in the narrow phase
+    // (t2_dyn_depth 141 -> 118 us).
+    size_t last_exit = gpc;
+    for (size_t pc = gpc + 1; pc < xpc; ++pc)
+        if (g.D[pc].op == U_OVF || g.D[pc].op == U_BRX) last_exit = pc;
     int ind = -1;
     int64_t step = 0;
-    for (size_t pc = gpc + 1; pc < xpc && ind < 0; ++pc) {
+    for (size_t pc = last_exit + 1; pc < xpc && ind < 0; ++pc) {
         const DOp &I = g.D[pc];
         if (I.op == U_ADDI && I.a == I.d && !(I.fl & UF_TA) && nwr[I.d / 8] == 1 && I.imm != 0 &&
             I.imm > -(int64_t(1) << 31) && I.imm < (int64_t(1) << 31))

@@ -11,7 +11,8 @@ import pytest
 import misaka_net_amd as mk
 from misaka_net_amd import _native as N
 from oracle import pyoracle as po
-from tisgen import loop_cases, random_network, stack_loop_network
+from tisgen import (ROT_BUDGETS, ROT_CAPS, loop_cases, random_network, rotated_seed_kwargs, rotated_stack_inputs,
+                    rotated_stack_loop_network, rotated_stack_loop_programs, stack_loop_network)
 
 pytestmark = pytest.mark.gpu
 
@@ -104,6 +105,52 @@ def test_loop_phases_bit_exact(gpu, monkeypatch, variant):
     for label, nodes, xs, kw in loop_cases(n=4096):
         xs = np.asarray(xs, np.int64)
         assert_same(mk.Network(nodes).compute_batch(xs, **kw), oracle(nodes, xs, **kw), f"{label} {variant}")
+
+
+# Loops that count before they push (tisgen.rotated_stack_loop_programs): the
+# native tier's induction register bumped ahead of a capacity exit gave
+# overflowing lanes one iteration's steps too many (emit_self_loop now takes
+# only bumps behind the last exit).  Every program in both orders, 2,048 lanes
+# (two or four sort tiles) that mix overflowing lanes, lanes leaving by the
+# branch and lanes that never loop, at capacities around every unguarded chunk
+# size and budgets inside the loop's guarded and unguarded parts; the variants
+# of test_loop_phases_bit_exact.  One module per capacity: the budgets share it.
+@pytest.mark.parametrize("variant", ["auto", "machine-early-exit", "pool64", "k2"])
+@pytest.mark.parametrize("name", [name for name, _ in rotated_stack_loop_programs()])
+def test_rotated_stack_loops_bit_exact(gpu, monkeypatch, name, variant):
+    if variant != "auto":
+        monkeypatch.setenv("MK_JIT_SHAPE", "machine")
+    if variant == "machine-early-exit":
+        monkeypatch.setenv("MK_JIT_POLICY", "8,12,16")
+    if variant == "pool64":
+        monkeypatch.setenv("MK_JIT_POOL", "64")
+    if variant == "k2":
+        monkeypatch.setenv("MK_JIT_POOL", "2")
+    nodes = dict(rotated_stack_loop_programs())[name]
+    xs = np.asarray(rotated_stack_inputs(2048), np.int64)
+    net = mk.Network(nodes)
+    overflows = 0
+    for cap in ROT_CAPS:
+        for budget in ROT_BUDGETS:
+            kw = {"stack_cap": cap, **({"budget": budget} if budget else {})}
+            ref = oracle(nodes, xs, **kw)
+            overflows += int(((ref[1] & N.MK_ST_REASON_MASK) == N.MK_ST_STACK_OVERFLOW).sum())
+            assert_same(net.compute_batch(xs, **kw), ref, f"{name} {variant} cap {cap} budget {budget}")
+    assert overflows > 0, name
+
+
+# The seeded networks of the same class (tisgen.rotated_stack_loop_network:
+# the counter bump first, in the middle or last in each loop body) on every
+# tier, capacities and budgets rotating as in
+# test_dynamic_stack_networks_bit_exact, with capacity 33.
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("seed", range(0, 30))
+def test_rotated_stack_networks_bit_exact(gpu, seed, mode):
+    rows, gen = rotated_stack_loop_network(seed)
+    xs = po.gen_inputs(seed + 5, 2048, **gen)
+    kw = rotated_seed_kwargs(seed)
+    got = mk.Network(rows).compute_batch(xs, mode=_m(mode), **kw)
+    assert_same(got, oracle(rows, xs, **kw), f"seed {seed}")
 
 
 # Both stack-slot layouts of the heavy kernel (wave-blocked / lane-major),
@@ -329,6 +376,29 @@ def test_machine_reason_counters(gpu, case):
     assert got[0] == int(sp.cpu().numpy().view(np.uint32).astype(np.int64).sum())
     if case != "plain":
         assert want[2 + {"budget": 1, "overflow": 2, "stop": 3}[case]] > 0, (case, want)
+    if case == "overflow":  # every lane, and so the summed steps, against the oracle (a table over the inputs 0..255)
+        x = po.gen_inputs(SEED, n, kind=N.MK_GEN_MASKED, mask=mask)
+        t_out, t_st, t_sp = oracle(nodes, np.arange(256, dtype=np.int64), **kw)
+        assert np.array_equal(out.cpu().numpy(), t_out[x]) and np.array_equal(s_, t_st[x])
+        assert np.array_equal(sp.cpu().numpy().view(np.uint32), t_sp[x])
+        assert got[0] == int(t_sp[x].astype(np.int64).sum())
+
+
+# Device statistics on a loop that counts before it pushes: the summed steps
+# (stats[0]) and the overflow count are the oracle's, lane by lane too.
+def test_rotated_stack_loop_device_stats(gpu):
+    n, cap = 1 << 16, 64
+    nodes = dict(rotated_stack_loop_programs())["swp_counter-rot"]
+    net = mk.Network(nodes)
+    assert net.plan(stack_cap=cap).startswith("tier=native") and "shape=machine" in net.plan(stack_cap=cap)
+    out, st, sp, stats = _device_run(net, n, gen=(N.MK_GEN_MASKED, 255), stack_cap=cap)
+    x = po.gen_inputs(SEED, n, kind=N.MK_GEN_MASKED, mask=255)
+    t_out, t_st, t_sp = oracle(nodes, np.arange(256, dtype=np.int64), stack_cap=cap)
+    over = (t_st[x] & N.MK_ST_REASON_MASK) == N.MK_ST_STACK_OVERFLOW
+    assert 0 < int(over.sum()) < n
+    assert np.array_equal(out, t_out[x]) and np.array_equal(st, t_st[x]) and np.array_equal(sp, t_sp[x])
+    assert stats[0] == int(t_sp[x].astype(np.int64).sum()) and stats[2] == n
+    assert stats[3 + N.MK_ST_STACK_OVERFLOW - 1] == int(over.sum())
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -390,7 +460,7 @@ def test_device_generator_matches_oracle(gpu):
     assert np.array_equal(d.cpu().numpy(), po.gen_inputs(SEED, n, offset=12345).astype(np.int32))
 
 
-def _device_run(net, n, *, in_tensor=None, in_kind=N.MK_IN_I32, gen=(N.MK_GEN_FULL, 0), offset=0, mode=None):
+def _device_run(net, n, *, in_tensor=None, in_kind=N.MK_IN_I32, gen=(N.MK_GEN_FULL, 0), offset=0, mode=None, **kw):
     import torch
 
     out = torch.empty(n, dtype=torch.int32, device="cuda")
@@ -400,7 +470,7 @@ def _device_run(net, n, *, in_tensor=None, in_kind=N.MK_IN_I32, gen=(N.MK_GEN_FU
     net.compute_device(n, out_ptr=out.data_ptr(), status_ptr=st.data_ptr(), steps_ptr=sp.data_ptr(),
                        stats_ptr=stats.data_ptr(), in_ptr=None if in_tensor is None else in_tensor.data_ptr(),
                        in_kind=in_kind, seed=SEED, gen_kind=gen[0], gen_mask=gen[1], offset=offset,
-                       stream=torch.cuda.current_stream().cuda_stream, mode=_m(mode))
+                       stream=torch.cuda.current_stream().cuda_stream, mode=_m(mode), **kw)
     torch.cuda.synchronize()
     return out.cpu().numpy(), st.cpu().numpy(), sp.cpu().numpy().view(np.uint32), stats.cpu().numpy()
 

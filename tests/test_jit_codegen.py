@@ -17,7 +17,8 @@ import misaka_net_amd as mk
 from misaka_net_amd.network import NodeSpec
 from oracle import pyoracle as po
 import schedcheck as sc
-from tisgen import census_classes, stack_loop_network, loop_cases, random_network
+from tisgen import (census_classes, stack_loop_network, loop_cases, random_network, rotated_seed_kwargs,
+                    rotated_stack_loop_cases, rotated_stack_loop_network)
 
 SEED = 0x4D49534B41
 
@@ -84,18 +85,20 @@ def run_lane(lib, i, xs, budget):
 def check_cases(tmp_path, cases, machine=False):
     """cases: [(label, nodes, xs, kw)] -- every case compiled and compared.
     ``machine``: the resumable (machine-shape) lane for every case."""
-    srcs, keep = [], []
+    srcs, keep, lane = [], [], {}
     for label, nodes, xs, kw in cases:
         try:
             src, ns = sc.jit_lane(nodes, stack_cap=kw.get("stack_cap"), stop_on_output=kw.get("stop_on_output", False),
                                   machine=machine)
         except sc.NotCompiled:
             continue  # tier 1 handles it; covered elsewhere
-        srcs.append((src, ns))
-        keep.append((label, nodes, xs, kw))
+        if (src, ns) not in lane:  # cases that differ in the budget only share a lane
+            lane[(src, ns)] = len(srcs)
+            srcs.append((src, ns))
+        keep.append((label, nodes, xs, kw, lane[(src, ns)]))
     assert keep, "no case compiled"
     lib = build_lanes(srcs, str(tmp_path / "lanes"))
-    for i, (label, nodes, xs, kw) in enumerate(keep):
+    for label, nodes, xs, kw, i in keep:
         got = run_lane(lib, i, xs, kw.get("budget") or (1 << 20))
         ref = po.OracleNet(nodes).compute_batch(xs, **kw)
         bad = np.nonzero((got[0] != ref[0]) | (got[1] != ref[1]) | (got[2] != ref[2]))[0]
@@ -203,6 +206,73 @@ def test_dynamic_stack_networks(tmp_path, block, machine):
             xs = po.gen_inputs(3, 256, kind=1, mask=255)
             cases.append((f"{cls}_{cap}", nodes, xs, {"stack_cap": cap} if cap else {}))
     assert len(check_cases(tmp_path, cases, machine)) >= 24
+
+
+def overflowed(status):
+    """Lanes the oracle ended by a stack overflow."""
+    return (status & mk._native.MK_ST_REASON_MASK) == mk._native.MK_ST_STACK_OVERFLOW
+
+
+def rotated_case_groups(cases, ref_of):
+    """{program: [(label, overflowing lanes, their largest oracle step count)]}
+    and the check that no program passes by never overflowing: some capacity
+    and budget of each has lanes that overflow, and one of them overflows past
+    the unguarded phases' largest chunk (32 iterations; an iteration retires
+    at most every line of the network once)."""
+    groups = {}
+    for label, nodes, xs, kw in cases:
+        st, sp = ref_of(label, nodes, xs, kw)[1:3]
+        ov = overflowed(st)
+        lines = sum(len([ln for ln in n[2].splitlines() if ln.strip()]) for n in nodes if n[1] == "program")
+        row = (label, int(ov.sum()), int(sp[ov].max()) if ov.any() else 0, lines)
+        groups.setdefault(label.split("/")[0], []).append(row)
+    for name, rows in groups.items():
+        over = [r for r in rows if r[1] > 0]
+        assert over, f"{name}: no capacity / budget with an overflowing lane"
+        assert any(steps > 33 * lines for _, _, steps, lines in over), f"{name}: no overflow past 32 iterations"
+    return groups
+
+
+# Loops that count before they push (tisgen.rotated_stack_loop_cases): the
+# induction register's bump ahead of a capacity exit.  A lane that overflows
+# inside an unguarded chunk reported its steps one iteration too high
+# (sub_push-rot at capacity 64, input 65: 197 for the oracle's 194; two PUSHes
+# per iteration, input 33: 134 for 130; the counter and the pushed value both
+# bumped first, capacities 33 / 64 / 200: 209 / 395 / 1211 for 203 / 389 /
+# 1205) until emit_self_loop took only bumps behind the last exit.
+@pytest.mark.parametrize("machine", [False, True])
+def test_rotated_stack_loops(tmp_path, machine):
+    cases = [(lbl, nodes, np.asarray(xs, np.int64), kw) for lbl, nodes, xs, kw in rotated_stack_loop_cases()]
+    groups = rotated_case_groups(cases, lambda lbl, nodes, xs, kw: po.OracleNet(nodes).compute_batch(xs, **kw))
+    assert len(groups) == 14 and all(len(rows) == 32 for rows in groups.values())
+    assert len(check_cases(tmp_path, cases, machine)) == len(cases)
+
+
+@pytest.mark.parametrize("machine", [False, True])
+@pytest.mark.parametrize("block", range(2))
+def test_rotated_stack_networks(tmp_path, block, machine):
+    # tisgen.rotated_stack_loop_network: the counter bump first, in the
+    # middle or last in every loop body of the seeded dynamic-stack networks
+    cases, overflowing = [], 0
+    for seed in range(block * 30, block * 30 + 30):
+        rows, gen = rotated_stack_loop_network(seed)
+        kw = rotated_seed_kwargs(seed)
+        xs = po.gen_inputs(seed + 5, 512, **gen)
+        overflowing += bool(overflowed(po.OracleNet(rows).compute_batch(xs, **kw)[1]).any())
+        cases.append((f"seed{seed}", rows, xs, kw))
+    assert overflowing >= 4, overflowing  # of 30 seeds: the test is about lanes that overflow
+    assert len(check_cases(tmp_path, cases, machine)) >= 24  # the others are tier 1's
+
+
+def test_stack_loop_network_rows_are_pinned():
+    # rotate= must not move what the seeded dynamic-stack tests have always
+    # checked: the rows and input kinds of seeds 0..89 without it, by digest
+    import hashlib
+
+    rows = repr([stack_loop_network(s) for s in range(90)]).encode()
+    assert hashlib.sha256(rows).hexdigest() == "c7bec21879c3f33f3cb32ee71035eee4e5d4111df6767554632db88fe89e8bf5"
+    moved = sum(rotated_stack_loop_network(s)[0] != stack_loop_network(s)[0] for s in range(90))
+    assert moved >= 45, moved  # and rotate=True does move the counter
 
 
 def test_shapes():

@@ -8,7 +8,7 @@ import pytest
 import misaka_net_amd as mk
 from oracle import pyoracle as po
 import schedcheck as sc
-from tisgen import random_network, stack_loop_network
+from tisgen import random_network, rotated_stack_loop_cases, rotated_stack_loop_network, stack_loop_network
 
 SEED = 0x4D49534B41
 
@@ -90,6 +90,20 @@ def test_dynamic_stack_networks():
         rows, gen = stack_loop_network(seed)
         xs = po.gen_inputs(seed + 5, 64, **gen)
         for cap, budget in ((None, None), (3, 200), (17, 1000), (64, 57)):
+            kw = {k: v for k, v in (("stack_cap", cap), ("budget", budget)) if v is not None}
+            same(rows, xs, **kw)
+
+
+def test_rotated_stack_loops():
+    # loops that count before they push (tisgen.rotated_stack_loop_cases and
+    # the seeded rotated networks): the host model keeps steps per micro-op,
+    # so the order of the bump and the capacity check is nothing to it
+    for label, nodes, xs, kw in rotated_stack_loop_cases():
+        same(nodes, np.asarray(xs, np.int64), **kw)
+    for seed in range(60):
+        rows, gen = rotated_stack_loop_network(seed)
+        xs = po.gen_inputs(seed + 5, 96, **gen)
+        for cap, budget in ((None, None), (3, 200), (17, 1000), (33, 300), (64, 57), (200, None)):
             kw = {k: v for k, v in (("stack_cap", cap), ("budget", budget)) if v is not None}
             same(rows, xs, **kw)
 

@@ -18,7 +18,7 @@ from oracle import pyoracle as po
 import schedcheck as sc
 from misaka_net_amd import _native as N
 from schedcheck import HANDOFF, HostSessions, NotCompiled
-from tisgen import random_network, stack_loop_network
+from tisgen import random_network, rotated_stack_loop_programs, stack_loop_network
 
 CALLS = 6
 
@@ -187,8 +187,6 @@ def _build_sessions(cases, path):
 
 
 def test_generated_session_lane(tmp_path):
-    import schedcheck as sc
-
     nets = [("example", mk.networks.example_network(), {}, (0, 0)),
             ("sample", mk.networks.sample_network(), {}, (0, 0)),
             ("countdown", mk.networks.countdown_network(), {"budget": 700}, (1, 1023)),
@@ -203,6 +201,15 @@ def test_generated_session_lane(tmp_path):
     for seed in range(12):
         rows, gen = stack_loop_network(seed)
         nets.append((f"stk{seed}", rows, {"budget": [100, 2000][seed % 2]}, (gen["kind"], gen["mask"])))
+    _check_session_lanes(tmp_path, nets)
+
+
+def _check_session_lanes(tmp_path, nets, calls=5):
+    """nets: [(label, nodes, kwargs, (input kind, mask))] -- the generated
+    session lane of each against the host model, call by call.  Returns the
+    labels that compiled."""
+    import schedcheck as sc
+
     cases, keep = [], []
     for label, nodes, kw, gen in nets:
         try:
@@ -220,7 +227,7 @@ def test_generated_session_lane(tmp_path):
         regs = np.zeros(max(1, nr) * n, np.int64)
         slots = np.full(max(1, ns) * n, 0x5A5A5A5A, np.int32)
         b = kw.get("budget") or (1 << 20)
-        for k in range(5):
+        for k in range(calls):
             row = po.gen_inputs(k * 31 + i, n, kind=gen[0], mask=gen[1])
             ref = host.call(row, budget=b)
             out, st, sp = np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.uint32)
@@ -231,6 +238,31 @@ def test_generated_session_lane(tmp_path):
             for a, r in zip((out, st, sp), ref):
                 bad = np.nonzero(a != r)[0]
                 assert not bad.size, (label, k, int(bad[0]), int(a[bad[0]]), int(r[bad[0]]))
+    return [k[0] for k in keep]
+
+
+# Sessions on loops that count before they push (tisgen.rotated_stack_loop_programs):
+# every call leaves entries on the stack, so a sequence of calls fills it and
+# one of them overflows inside the loop, past its 32nd iteration.  The host
+# model against the oracle's sessions, call by call (steps of every call), and
+# the generated session lane against the host model.
+@pytest.mark.parametrize("name", ["sub_push-rot", "swp_counter-rot", "two_stacks-rot", "sub_push-ctl"])
+def test_rotated_stack_loop_sessions(tmp_path, name):
+    nodes = dict(rotated_stack_loop_programs())[name]
+    n, cap, calls, mask = 24, 200, 6, 255
+    ref = po.OracleSessions(po.OracleNet(nodes), n, stack_cap=cap)
+    first, deep = [], 0
+    for k in range(calls):  # run_pair's inputs
+        _, rs, rp = ref.compute(po.gen_inputs(7 * 7919 + k, n, kind=1, mask=mask))
+        ov = (rs & N.MK_ST_REASON_MASK) == N.MK_ST_STACK_OVERFLOW
+        first.append(int(ov.sum()))
+        deep = max(deep, int(rp[ov].max()) if ov.any() else 0)
+        ref.cancel()
+    lines = sum(len(nd[2].splitlines()) for nd in nodes if nd[1] == "program")
+    assert sum(first) > 0 and deep > 33 * lines, (first, deep)
+    checked, _ = run_pair(nodes, n, stack_cap=cap, seed=7, calls=calls, kind=1, mask=mask)
+    assert checked == n * calls
+    assert _check_session_lanes(tmp_path, [(name, nodes, {"stack_cap": cap}, (1, mask))], calls=8) == [name]
 
 
 def test_session_modules_compile_for_gfx950(tmp_path):

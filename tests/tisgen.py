@@ -206,13 +206,20 @@ def loop_cases(n: int = 512, seed: int = 7):
 from misaka_net_amd.networks import census_classes  # noqa: E402,F401  (defined with the bench workloads)
 
 
-def stack_loop_network(seed: int):
+def stack_loop_network(seed: int, rotate: bool = False):
     """Networks whose stack depths follow the data (the schedule compiler's
     dynamic stacks): loops with input-dependent trip counts that push and pop
     on 1-3 stacks, pops that may outnumber pushes (the POP then blocks), a
     second node popping what the first pushes (cross-node blocking), and
     values that reach the output (sums of popped values).  Returns
-    (rows, gen kwargs for oracle.gen_inputs)."""
+    (rows, gen kwargs for oracle.gen_inputs).
+
+    ``rotate``: the counter's ``SUB step`` lands at a random place among the
+    body's pushes and pops -- first, in the middle or last -- instead of
+    always last, so loops count before they push (the native tier's induction
+    register is then bumped ahead of a capacity exit).  Without it the rows
+    of a seed are the ones they always were
+    (test_jit_codegen.py test_stack_loop_network_rows_are_pinned)."""
     r = random.Random(seed)
     ns = r.randint(1, 3)
     stacks = [f"s{k}" for k in range(ns)]
@@ -224,21 +231,26 @@ def stack_loop_network(seed: int):
     for k in range(r.randint(1, 3)):
         s = r.choice(stacks)
         lab = f"L{k}"
-        body = []
+        body = []  # groups of lines; ACC is the counter between groups
         for _ in range(r.randint(1, 3)):
             c = r.random()
             if c < 0.45:
-                body.append(f"PUSH ACC, {r.choice(stacks)}")
+                body.append([f"PUSH ACC, {r.choice(stacks)}"])
             elif c < 0.6:
-                body.append(f"PUSH {r.randint(-5, 5)}, {r.choice(stacks)}")
+                body.append([f"PUSH {r.randint(-5, 5)}, {r.choice(stacks)}"])
             elif c < 0.8 and not consumer:
-                body.append(f"POP {r.choice(stacks)}, NIL")
+                body.append([f"POP {r.choice(stacks)}, NIL"])
             else:
                 # accumulate a popped value into BAK (ACC is the counter)
-                body += ["SWP", f"PUSH ACC, {s}", f"POP {r.choice(stacks)}, ACC", "SWP"]
+                body.append(["SWP", f"PUSH ACC, {s}", f"POP {r.choice(stacks)}, ACC", "SWP"])
         step = r.choice([1, 1, 2, 3])
         jump = r.choice(["JGZ", "JGZ", "JNZ"]) if step == 1 else "JGZ"
-        lines += [f"{lab}: " + body[0]] + body[1:] + [f"SUB {step}", f"{jump} {lab}"]
+        at = len(body)
+        if rotate:
+            at = r.choice([0, len(body) // 2, len(body)])  # first, middle, last
+        body.insert(at, [f"SUB {step}"])
+        flat = [ln for grp in body for ln in grp]
+        lines += [f"{lab}: " + flat[0]] + flat[1:] + [f"{jump} {lab}"]
         if r.random() < 0.5:
             lines += ["SWP", "SAV"]  # the next loop counts from the running value
     if consumer:
@@ -252,3 +264,96 @@ def stack_loop_network(seed: int):
     rows += [(s, "stack", "") for s in stacks]
     r.shuffle(rows)
     return rows, dict(kind=1, mask=r.choice([15, 63, 255]))
+
+
+# ---- stack loops that count before they push ----------------------------------
+# The native tier reads a lane's trip count off an induction register
+# (tis_jit.cpp emit_self_loop).  A loop whose counter bump comes before a PUSH
+# that can overflow has taken the bump when the capacity exit drops the lane:
+# only bumps after the last exit count iterations completed.  Every program
+# here comes in two orders -- "rot" (the counter first) and "ctl" (the
+# counter last, what loop_cases and stack_loop_network emit).
+ROT_CAPS = (3, 8, 16, 17, 33, 64, 65, 200)  # around every unguarded chunk size (4..32, and twice that)
+ROT_BUDGETS = (None, 57, 300, 1000)         # none, inside the guarded part, inside the unguarded part
+
+
+def _rot_programs():
+    S = ("s", "stack", "")
+    T = ("t", "stack", "")
+    one = lambda text, *st: [("a", "program", text)] + list(st)  # noqa: E731
+    fill = "IN ACC\nSAV\nF: PUSH ACC, s\nSUB 1\nJGZ F\nSWP\n"
+    pusher = ("b", "program", "M: MOV R0, ACC\nPUSH ACC, s\nJMP M")
+    return [
+        ("sub_push", "rot", one("IN ACC\nL: SUB 1\nPUSH ACC, s\nJGZ L\nPOP s, ACC\nOUT ACC", S)),
+        ("sub_push", "ctl", one("IN ACC\nL: PUSH ACC, s\nSUB 1\nJGZ L\nPOP s, ACC\nOUT ACC", S)),
+        ("add2_push_jlz", "rot", one("IN ACC\nL: ADD 2\nPUSH ACC, s\nJLZ L\nPOP s, ACC\nOUT ACC", S)),
+        ("add2_push_jlz", "ctl", one("IN ACC\nL: PUSH ACC, s\nADD 2\nJLZ L\nPOP s, ACC\nOUT ACC", S)),
+        ("sub_push_push", "rot", one("IN ACC\nL: SUB 1\nPUSH ACC, s\nPUSH 3, s\nJGZ L\nPOP s, ACC\nOUT ACC", S)),
+        ("sub_push_push", "ctl", one("IN ACC\nL: PUSH ACC, s\nPUSH 3, s\nSUB 1\nJGZ L\nPOP s, ACC\nOUT ACC", S)),
+        # two registers bumped ahead of the PUSH: the counter and, in BAK, the value pushed
+        ("swp_counter", "rot", one("IN ACC\nSAV\nL: SUB 1\nSWP\nADD 1\nPUSH ACC, s\nSWP\nJGZ L\nSWP\nOUT ACC", S)),
+        ("swp_counter", "ctl", one("IN ACC\nSAV\nL: SWP\nADD 1\nPUSH ACC, s\nSWP\nSUB 1\nJGZ L\nSWP\nOUT ACC", S)),
+        # a POP loop (the empty-check exit) behind a fill loop that overflows
+        ("fill_pop", "rot", one(fill + "L: SUB 1\nPOP s, NIL\nJGZ L\nOUT ACC", S)),
+        ("fill_pop", "ctl", one(fill + "L: POP s, NIL\nSUB 1\nJGZ L\nOUT ACC", S)),
+        # the counter in node a, the PUSH in node b
+        ("two_nodes", "rot", [("a", "program", "IN ACC\nL: SUB 1\nMOV ACC, b:R0\nJGZ L\nOUT ACC"), pusher, S]),
+        ("two_nodes", "ctl", [("a", "program", "IN ACC\nL: MOV ACC, b:R0\nSUB 1\nJGZ L\nOUT ACC"), pusher, S]),
+        # two stacks, the second three entries ahead: it overflows first, after
+        # the first one's depth register took its bump
+        ("two_stacks", "rot", one("IN ACC\nPUSH 1, t\nPUSH 1, t\nPUSH 1, t\nL: SUB 1\nPUSH ACC, s\nPUSH ACC, t\nJGZ L\n"
+                                  "POP s, ACC\nOUT ACC", S, T)),
+        ("two_stacks", "ctl", one("IN ACC\nPUSH 1, t\nPUSH 1, t\nPUSH 1, t\nL: PUSH ACC, s\nPUSH ACC, t\nSUB 1\nJGZ L\n"
+                                  "POP s, ACC\nOUT ACC", S, T)),
+    ]
+
+
+def rotated_stack_inputs(n: int | None = None, seed: int = 11):
+    """-5..259 dense, +-1000 and the _edge_inputs edges: with ROT_CAPS every
+    wave mixes lanes that overflow, lanes that leave by the branch and lanes
+    that never enter the loop.  ``n``: that many lanes, every value present,
+    in a seeded shuffle."""
+    edges = [0, 1, -1, 2**30, -(2**30), 2**30 + 1, -(2**30) - 1, 2**31 - 1, -(2**31), 2**31 - 2, -(2**31) + 1]
+    xs = list(range(-5, 260)) + [1000, -1000] + edges
+    if n is not None:
+        assert n >= len(xs)
+        xs = (xs * (n // len(xs) + 1))[:n]
+        random.Random(seed).shuffle(xs)
+    return xs
+
+
+def rotated_stack_loop_programs():
+    """[(name, nodes)]: name is '<program>-rot' or '<program>-ctl'."""
+    return [(f"{name}-{order}", nodes) for name, order, nodes in _rot_programs()]
+
+
+def rotated_stack_loop_cases(n: int | None = None, caps=ROT_CAPS, budgets=ROT_BUDGETS):
+    """[(label, nodes, inputs, kwargs)] like loop_cases: every program of
+    rotated_stack_loop_programs at every capacity and budget; the label is
+    '<program>-<order>/cap<capacity>/b<budget>'."""
+    xs = rotated_stack_inputs(n)
+    cases = []
+    for name, nodes in rotated_stack_loop_programs():
+        for cap in caps:
+            for budget in budgets:
+                kw = {"stack_cap": cap}
+                if budget is not None:
+                    kw["budget"] = budget
+                cases.append((f"{name}/cap{cap}/b{budget}", nodes, xs, kw))
+    return cases
+
+
+def rotated_stack_loop_network(seed: int):
+    """stack_loop_network with the counter bump at a random place in each
+    loop's body, and inputs 0..255 whatever mask the seed drew: trip counts
+    then pass every capacity of rotated_seed_kwargs."""
+    rows, gen = stack_loop_network(seed, rotate=True)
+    return rows, dict(gen, mask=255)
+
+
+def rotated_seed_kwargs(seed: int) -> dict:
+    """Capacity and budget of a seeded rotated network: the rotation of the
+    seeded dynamic-stack tests, with capacity 33 (just past the largest
+    unguarded chunk) added."""
+    kw = dict(budget=[None, 57, 300, 2000][seed % 4], stack_cap=[None, 3, 17, 33, 64, 200][seed % 6])
+    return {k: v for k, v in kw.items() if v is not None}
