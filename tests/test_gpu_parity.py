@@ -1,6 +1,7 @@
 """GPU executor (HIP, via the C ABI) against the CPU oracle: bit-exact
 out/status/steps on seeded inputs, plus size-independent properties at the
 BASELINE.json sizes."""
+import functools
 import os
 import re
 import threading
@@ -11,8 +12,9 @@ import pytest
 import misaka_net_amd as mk
 from misaka_net_amd import _native as N
 from oracle import pyoracle as po
-from tisgen import (ROT_BUDGETS, ROT_CAPS, loop_cases, random_network, rotated_seed_kwargs, rotated_stack_inputs,
-                    rotated_stack_loop_network, rotated_stack_loop_programs, stack_loop_network)
+from tisgen import (ROT_BUDGETS, ROT_CAPS, deep_seed_kwargs, deep_stack_inputs, deep_stack_network, loop_cases,
+                    random_network, rotated_seed_kwargs, rotated_stack_inputs, rotated_stack_loop_network,
+                    rotated_stack_loop_programs, stack_loop_network)
 
 pytestmark = pytest.mark.gpu
 
@@ -302,6 +304,156 @@ def test_dynamic_stack_networks_bit_exact(gpu, seed, mode):
     kw = {k: v for k, v in kw.items() if v is not None}
     got = mk.Network(rows).compute_batch(xs, mode=_m(mode), **kw)
     assert_same(got, oracle(rows, xs, **kw), f"seed {seed}")
+
+
+# ---- deep static stacks (tisgen.deep_stack_network) ---------------------------
+# Stacks whose depths the schedule compiler knows, deep enough to spill:
+# stacks that share slot ranges and stacks that interfere (tis_sched.cpp
+# share_slots), branches on the input whose arms use the stacks in different
+# orders and to different depths (waves diverge while slots are live), stacks
+# left half-drained, a second node popping the first one's stack.  613 lanes:
+# nine waves of one thread per input and a partial one (the light kernel: 4
+# lanes per thread, a ragged tail), every seventh input 0 so each wave mixes
+# the three sign classes.  One hiprtc compile per network and setting is what
+# a case costs.
+DEEP_N = 613
+DEEP_BIG = (0, 3, 5, 7, 9, 12)  # big=True seeds: split, plain HBM and two-wave LDS plans past 320 slots
+DEEP_HOMES = [(seed, False) for seed in range(20)] + [(seed, True) for seed in DEEP_BIG]
+
+
+@functools.lru_cache(maxsize=None)
+def _deep_case(seed, big=False, budget=None, stack_cap=None):
+    """(rows, inputs, the oracle's result): computed once, shared by every
+    setting that runs the network."""
+    rows = deep_stack_network(seed, big=big)
+    xs = deep_stack_inputs(seed, DEEP_N)
+    kw = {k: v for k, v in (("budget", budget), ("stack_cap", stack_cap)) if v is not None}
+    return rows, xs, oracle(rows, xs, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def _deep_auto_net(seed, big=False):
+    """The network on the default path with no knob set (compiled once)."""
+    return mk.Network(deep_stack_network(seed, big=big))
+
+
+def _native(net, **kw):
+    plan = net.plan(**kw)
+    assert plan.startswith("tier=native"), plan  # a fall to tier 2 (compile bound) fails the test
+    return plan
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("seed", range(0, 40))
+def test_deep_stack_networks_bit_exact(gpu, seed, mode):
+    kw = deep_seed_kwargs(seed)
+    rows, xs, ref = _deep_case(seed, False, kw.get("budget"), kw.get("stack_cap"))
+    net = mk.Network(rows)
+    if mode == "auto":
+        _native(net, **({"stack_cap": kw["stack_cap"]} if "stack_cap" in kw else {}))
+    assert_same(net.compute_batch(xs, mode=_m(mode), **kw), ref, f"deep seed {seed} {kw}")
+
+
+# Every home of the heavy kernel's slots (HBM wave-blocked and lane-major,
+# LDS, the LDS/HBM split the loader picks by itself) and the light kernel's
+# seeds on the heavy one.
+DEEP_HOME_ENV = {"blocked": {"MK_JIT_LDS_SLOTS": "0", "MK_JIT_SLOT_LAYOUT": "blocked"},
+                 "lane": {"MK_JIT_LDS_SLOTS": "0", "MK_JIT_SLOT_LAYOUT": "lane"},
+                 "lds": {"MK_JIT_LDS_SLOTS": "163840"}, "auto": {}, "heavy16": {"MK_JIT_HEAVY_OPS": "16"}}
+
+
+@pytest.mark.parametrize("home", list(DEEP_HOME_ENV))
+@pytest.mark.parametrize("seed,big", DEEP_HOMES)
+def test_deep_stack_slot_homes(gpu, monkeypatch, seed, big, home):
+    for k, v in DEEP_HOME_ENV[home].items():
+        monkeypatch.setenv(k, v)
+    rows, xs, ref = _deep_case(seed, big)
+    net = _deep_auto_net(seed, big) if home == "auto" else mk.Network(rows)
+    plan = _native(net)
+    if home == "heavy16":
+        assert "shape=stream-heavy" in plan, plan
+    if home in ("blocked", "lane") and "shape=stream-heavy" in plan:
+        assert "shape=stream-heavy " in plan, plan  # every slot in HBM
+    assert_same(net.compute_batch(xs), ref, f"deep seed {seed} big={big} {home}")
+
+
+def test_deep_stack_shape_coverage(gpu):
+    # the default path of DEEP_HOMES reaches every kernel and slot home, and
+    # a register plan of more_waves
+    plans = [_native(_deep_auto_net(seed, big)) for seed, big in DEEP_HOMES]
+    shapes = {p.split("shape=")[1].split()[0] for p in plans}
+    assert {"stream", "stream-heavy", "stream-heavy-lds", "stream-heavy-split"} <= shapes, shapes
+    waves = [p.split("stack_plans=")[1].split()[0] for p in plans if "stack_plans=" in p]
+    assert any(e.startswith("w") and not e.endswith("-rejected") for w in waves for e in w.split(";")), waves
+
+
+# Every stack in a range of its own (MK_SCHED_SHARE=0) and the shared ranges
+# of the default: both are the oracle's.
+@pytest.mark.parametrize("seed", range(0, 20))
+def test_deep_stack_sharing_off(gpu, monkeypatch, seed):
+    rows, xs, ref = _deep_case(seed)
+    shared = _deep_auto_net(seed)
+    assert_same(shared.compute_batch(xs), ref, f"deep seed {seed} shared")
+    monkeypatch.setenv("MK_SCHED_SHARE", "0")
+    own = mk.Network(rows)
+    _native(own)
+    assert_same(own.compute_batch(xs), ref, f"deep seed {seed} unshared")
+
+
+# The machine shape: the tile-sorted kernel by default (slots at
+# ts_rounds_slots), two lanes per thread, the smallest lane pool, and the
+# pool-less kernel leaving loops early.
+@pytest.mark.parametrize("variant,seed", [("default", s) for s in range(20)] +
+                         [(v, s) for v in ("k2", "pool64", "8,12,16") for s in range(10)])
+def test_deep_stack_machine_shape(gpu, monkeypatch, variant, seed):
+    monkeypatch.setenv("MK_JIT_SHAPE", "machine")
+    if variant == "k2":
+        monkeypatch.setenv("MK_JIT_POOL", "2")
+    if variant == "pool64":
+        monkeypatch.setenv("MK_JIT_POOL", "64")
+    if variant == "8,12,16":
+        monkeypatch.setenv("MK_JIT_POLICY", variant)
+    rows, xs, ref = _deep_case(seed)
+    net = mk.Network(rows)
+    assert "shape=machine" in _native(net)
+    assert_same(net.compute_batch(xs), ref, f"deep seed {seed} machine {variant}")
+
+
+# Chunked launches of the heavy kernel (MK_JIT_SLOT_BYTES=1: 64 inputs per
+# launch) on networks with slots in HBM: no stale slot crosses a chunk; the
+# counters add up over the chunks.
+@pytest.mark.parametrize("seed,big", [(1, False), (3, True), (5, True), (7, True), (12, True)])
+def test_deep_stack_chunked_launches(gpu, monkeypatch, seed, big):
+    import torch
+
+    monkeypatch.setenv("MK_JIT_SLOT_BYTES", "1")
+    rows, xs, ref = _deep_case(seed, big)
+    net = mk.Network(rows)
+    assert "shape=stream-heavy" in _native(net)
+    assert_same(net.compute_batch(xs), ref, f"deep seed {seed} big={big} chunked")
+    out, st, sp, stats = _device_run(net, DEEP_N, in_tensor=torch.from_numpy(xs).cuda(), in_kind=N.MK_IN_I64)
+    assert np.array_equal(out, ref[0]) and np.array_equal(st, ref[1]) and np.array_equal(sp, ref[2])
+    assert stats[0] == int(ref[2].astype(np.int64).sum()) and stats[2] == DEEP_N
+
+
+# The POP runs as plain loops (MK_JIT_PREFETCH=0) give what the pipelined ones give.
+@pytest.mark.parametrize("seed", range(0, 10))
+def test_deep_stack_pipelined_pops_off(gpu, monkeypatch, seed):
+    monkeypatch.setenv("MK_JIT_PREFETCH", "0")
+    rows, xs, ref = _deep_case(seed)
+    net = mk.Network(rows)
+    _native(net)
+    assert_same(net.compute_batch(xs), ref, f"deep seed {seed} prefetch off")
+
+
+# The session form: 2-3 calls per pass, stacks filled across calls, on the
+# native session tier; budget slices of 3000 leave calls open, resumed twice.
+@pytest.mark.parametrize("seed", range(0, 10))
+def test_deep_stack_sessions(gpu, seed):
+    rows = deep_stack_network(seed, session=True)
+    seqs = np.stack([deep_stack_inputs(seed + 100 * k, DEEP_N) for k in range(4)])
+    g, _ = _session_calls(rows, seqs, resumes=2, budget=3000)
+    assert g.plan().startswith("tier=native"), g.plan()
 
 
 # The census classes whose depths follow the data, at their bench size

@@ -17,8 +17,9 @@ import misaka_net_amd as mk
 from misaka_net_amd.network import NodeSpec
 from oracle import pyoracle as po
 import schedcheck as sc
-from tisgen import (census_classes, stack_loop_network, loop_cases, random_network, rotated_seed_kwargs,
-                    rotated_stack_loop_cases, rotated_stack_loop_network)
+from tisgen import (census_classes, deep_seed_kwargs, deep_stack_inputs, deep_stack_network, deep_stack_peaks,
+                    stack_loop_network, loop_cases, random_network, rotated_seed_kwargs, rotated_stack_loop_cases,
+                    rotated_stack_loop_network)
 
 SEED = 0x4D49534B41
 
@@ -273,6 +274,91 @@ def test_stack_loop_network_rows_are_pinned():
     assert hashlib.sha256(rows).hexdigest() == "c7bec21879c3f33f3cb32ee71035eee4e5d4111df6767554632db88fe89e8bf5"
     moved = sum(rotated_stack_loop_network(s)[0] != stack_loop_network(s)[0] for s in range(90))
     assert moved >= 45, moved  # and rotate=True does move the counter
+
+
+# ---- deep static stacks (tisgen.deep_stack_network): spilled entries, shared slots
+
+def test_deep_stack_network_rows_are_pinned():
+    # the rows of seeds 0..59 in every form, by digest: the share / interfere
+    # fractions below and the GPU tests' shape coverage are properties of
+    # these programs
+    import hashlib
+
+    rows = repr([deep_stack_network(s, **kw) for kw in ({}, {"session": True}, {"big": True}) for s in range(60)])
+    digest = hashlib.sha256(rows.encode()).hexdigest()
+    assert digest == "df7ec14c93433940320bcdb30c8fb446602e0e5d680a58a8e48b3483f07a88bf"
+
+
+def _deep_slots(rows, monkeypatch):
+    """(slots with sharing on, slots with it off)"""
+    monkeypatch.setenv("MK_SCHED_SHARE", "1")
+    on = sc.jit_lane(rows)[1]
+    monkeypatch.setenv("MK_SCHED_SHARE", "0")
+    off = sc.jit_lane(rows)[1]
+    monkeypatch.delenv("MK_SCHED_SHARE")
+    return on, off
+
+
+def test_deep_stack_networks_reach_the_placement_machinery(monkeypatch):
+    # What the generator is for: every seed on the native tier with static
+    # slots; at least a fifth of the seeds with stacks that share slots, and
+    # at least a fifth with spilled stacks that may not (the same count
+    # either way, and more slots than the deepest stack has entries: two or
+    # more stacks spill); both stream kernels.  Seeds 0..59 measure 28 %
+    # sharing and 53 % interfering.
+    shared = interfering = 0
+    shapes = set()
+    for seed in range(60):
+        rows = deep_stack_network(seed)
+        tier, shape = sc.tier(rows)  # raises nothing, declines nothing
+        assert tier == "native", (seed, tier, shape)
+        shapes.add(shape)
+        on, off = _deep_slots(rows, monkeypatch)
+        assert on <= off < 1024, (seed, on, off)  # static: a dynamic stack takes the capacity
+        shared += on < off
+        interfering += on == off and off > max(deep_stack_peaks(seed).values())
+    assert shared >= 12 and interfering >= 12, (shared, interfering)  # 20 % of 60
+    assert {"stream", "stream-heavy"} <= shapes, shapes
+
+
+def _deep_cases(seeds, n=60):
+    """[(label, nodes, inputs, kwargs)]: the seeded inputs (every seventh 0)
+    and 0, 1, -1, 2^31 - 1, so both arms of every branch run."""
+    return [(f"deep{seed}", deep_stack_network(seed),
+             np.concatenate([deep_stack_inputs(seed, n), np.asarray([0, 1, -1, 2**31 - 1], np.int64)]),
+             deep_seed_kwargs(seed)) for seed in seeds]
+
+
+def test_deep_stack_cases_end_every_way():
+    # across the seed set the capacities and budgets of deep_seed_kwargs end
+    # lanes by stack overflow and by budget, and leave others quiescent
+    reasons = set()
+    for _, nodes, xs, kw in _deep_cases(range(120)):
+        st = po.OracleNet(nodes).compute_batch(xs, **kw)[1]
+        reasons |= set((st & mk._native.MK_ST_REASON_MASK).tolist())
+    assert {mk._native.MK_ST_STACK_OVERFLOW, mk._native.MK_ST_BUDGET, mk._native.MK_ST_QUIESCENT} <= reasons, reasons
+
+
+# The generated lanes of seeds 0..119, stream and machine shape, with slot
+# sharing on and off: a miscoloured pair of stacks, a rolled run whose slot
+# expression is wrong after renumbering or a branch arm using a shared range
+# for the other stack shows here as a wrong output.
+@pytest.mark.parametrize("share", ["1", "0"])
+@pytest.mark.parametrize("machine", [False, True])
+@pytest.mark.parametrize("block", range(4))
+def test_deep_stack_networks(tmp_path, monkeypatch, block, machine, share):
+    monkeypatch.setenv("MK_SCHED_SHARE", share)
+    cases = _deep_cases(range(block * 30, block * 30 + 30))
+    assert len(check_cases(tmp_path, cases, machine)) == len(cases)  # none declined
+
+
+# The spill thresholds the loader's register plans choose among
+# (MK_SCHED_SOFT_REGS; tune_lds_auto and more_waves recompile with them).
+@pytest.mark.parametrize("soft", [8, 16, 40, 64])
+def test_deep_stack_networks_spill_thresholds(tmp_path, monkeypatch, soft):
+    monkeypatch.setenv("MK_SCHED_SOFT_REGS", str(soft))
+    cases = _deep_cases(range(40))
+    assert len(check_cases(tmp_path, cases)) == len(cases)
 
 
 def test_shapes():

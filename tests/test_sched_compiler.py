@@ -8,7 +8,8 @@ import pytest
 import misaka_net_amd as mk
 from oracle import pyoracle as po
 import schedcheck as sc
-from tisgen import random_network, rotated_stack_loop_cases, rotated_stack_loop_network, stack_loop_network
+from tisgen import (deep_seed_kwargs, deep_stack_inputs, deep_stack_network, random_network, rotated_stack_loop_cases,
+                    rotated_stack_loop_network, stack_loop_network)
 
 SEED = 0x4D49534B41
 
@@ -159,3 +160,16 @@ def test_slot_sharing_is_safe(shape):
     slots = sc.jit_lane(nodes)[1]
     own = (D - 23) * 2  # each stack's spilled depths, unshared
     assert (slots < own) == (shape != "interleaved"), (shape, slots)
+
+
+# The seeded deep static stacks (tisgen.deep_stack_network: spilled entries,
+# stacks that share slots and stacks that interfere, branches whose arms use
+# them in different orders, a second node popping the first one's stack) on
+# the host model, with sharing on and off, budgets and capacities rotating.
+@pytest.mark.parametrize("share", ["1", "0"])
+def test_deep_stack_networks(monkeypatch, share):
+    monkeypatch.setenv("MK_SCHED_SHARE", share)
+    for seed in range(120):
+        xs = deep_stack_inputs(seed, 60)
+        xs[:4] = [0, 1, -1, 2147483647]
+        same(deep_stack_network(seed), xs, **deep_seed_kwargs(seed))

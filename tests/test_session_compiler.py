@@ -18,7 +18,7 @@ from oracle import pyoracle as po
 import schedcheck as sc
 from misaka_net_amd import _native as N
 from schedcheck import HANDOFF, HostSessions, NotCompiled
-from tisgen import random_network, rotated_stack_loop_programs, stack_loop_network
+from tisgen import deep_stack_network, random_network, rotated_stack_loop_programs, stack_loop_network
 
 CALLS = 6
 
@@ -126,6 +126,26 @@ def test_stack_loop_networks(seed):
                  kind=gen.get("kind", 0), mask=gen.get("mask", 0))
     except NotCompiled:
         pytest.skip("not compilable")
+
+
+# Deep static stacks in sessions (tisgen.deep_stack_network(session=True)):
+# 2-3 calls per pass through the program, stacks that stay filled across a
+# call (the U_YIELD successors of share_slots), every stack drained before
+# the program wraps.  Every seed compiles.
+@pytest.mark.parametrize("budget", [None, 3000])
+@pytest.mark.parametrize("seed", range(40))
+def test_deep_stack_sessions(seed, budget):
+    nodes = deep_stack_network(seed, session=True)
+    n = 16
+    checked, _ = run_pair(nodes, n, budget=budget, seed=seed)
+    assert checked == n * CALLS
+
+
+def test_deep_stack_session_lanes(tmp_path):
+    # the generated session lane of the same networks against the host model
+    nets = [(f"deep{seed}", deep_stack_network(seed, session=True), {"budget": [None, 3000][seed % 2]}, (0, 0))
+            for seed in range(40)]
+    assert len(_check_session_lanes(tmp_path, nets, calls=7)) == len(nets)
 
 
 # ---- the generated session lane (tis_jit.cpp, machine shape) compiled with g++,

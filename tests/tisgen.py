@@ -8,6 +8,10 @@ Two generators:
   * ``mutated_line`` -- text-level mutations of valid lines (whitespace
     classes incl. \\v and \\f, case, commas, signs, labels, comments) for
     parser accept/reject/error-text parity.
+
+Further down: loop shapes of the native machine kernel, networks whose stack
+depths follow the data (``stack_loop_network``) and deep static stacks
+(``deep_stack_network``: spilled entries, shared and interfering slots).
 """
 from __future__ import annotations
 
@@ -264,6 +268,230 @@ def stack_loop_network(seed: int, rotate: bool = False):
     rows += [(s, "stack", "") for s in stacks]
     r.shuffle(rows)
     return rows, dict(kind=1, mask=r.choice([15, 63, 255]))
+
+
+# ---- deep static stacks: constant trip counts, spilled entries, shared slots ------
+# Run lengths and depths around every threshold of the placement machinery:
+# the register-resident entries (24), the pipelined POP loop (64 pops, tails
+# of reps % 2) and, with big=True, slot counts past a two-wave LDS share.
+DEEP_DEPTHS = (3, 23, 24, 25, 40, 63, 64, 65, 95, 96, 97, 130)
+DEEP_BIG_DEPTHS = (160, 200)
+DEEP_WIDE = ("2147483647", "-2147483648", "4294967301", "1073741824")
+
+
+class _DeepGen:
+    """One node's program text.  The running value lives in BAK, the loop
+    counter in ACC; ``hi`` / ``lo`` bound each stack's depth over every path
+    to here (they differ only behind a branch whose arms end at different
+    depths)."""
+
+    def __init__(self, r, me, stacks, limit, depths):
+        self.r, self.me, self.limit, self.depths = r, me, limit, depths
+        self.lines, self.nlab = [], 0
+        self.hi = {s: 0 for s in stacks}
+        self.lo = dict(self.hi)
+        self.peak = dict(self.hi)
+
+    def label(self):
+        self.nlab += 1
+        return f"T{self.nlab}"
+
+    def push(self, s, d=None):
+        r = self.r
+        room = self.limit - self.hi[s]
+        fits = [x for x in self.depths if x <= room]
+        if d is None:
+            if not fits:
+                return False
+            d = r.choice(fits + [x for x in fits if x >= 40])  # spilling depths twice as often
+        t = self.label()
+        c = r.random()
+        # wide steps: the pushed values truncate to int32, a POP must sign-extend
+        k = r.choice(DEEP_WIDE) if 0.2 <= c < 0.45 else str(r.choice([1, 1, 3, 7, -2, -11]))
+        src = "ACC"
+        if c < 0.2:  # U_STI (the running value still moves: a loop of constants alone would be generalised)
+            src = r.choice(["-1", "5", "2147483647", "-2147483648", str(r.randint(-99, 99))])
+        self.lines += [f"MOV {d}, ACC", f"{t}: SWP", f"ADD {k}", f"PUSH {src}, {s}", "SWP", "SUB 1", f"JGZ {t}"]
+        self.hi[s] += d
+        self.lo[s] += d
+        self.peak[s] = max(self.peak[s], self.hi[s])
+        return True
+
+    def pop(self, s, d=None, nil=None):
+        """run = 3 * run + popped (odd multiplier: every popped value, in its
+        order, stays in the low 32 bits -- networks.pipeline_program); no
+        store in the loop, so it may become the pipelined POP loop."""
+        r = self.r
+        if self.lo[s] == 0:
+            return False
+        if d is None:
+            d = self.lo[s] if r.random() < 0.6 else r.randint(1, self.lo[s])
+        if nil is None:
+            nil = r.random() < 0.15
+        t, me = self.label(), self.me
+        if nil:
+            self.lines += [f"MOV {d}, ACC", f"{t}: SWP", "ADD 1", f"POP {s}, NIL", "SWP", "SUB 1", f"JGZ {t}"]
+        else:
+            self.lines += [f"MOV {d}, ACC", f"{t}: SWP", f"MOV ACC, {me}:R3", f"POP {s}, ACC", f"MOV ACC, {me}:R2",
+                           "MOV R3, ACC", f"MOV ACC, {me}:R3", "ADD ACC", "ADD R3", "ADD R2", "SWP", "SUB 1",
+                           f"JGZ {t}"]
+        self.hi[s] -= d
+        self.lo[s] -= d
+        return True
+
+    def block(self, stacks):
+        """2-3 runs: one stack filled and drained (sequential), or random
+        pushes and pops over ``stacks`` (nested, interleaved, half-drained)."""
+        r = self.r
+        if r.random() < 0.35:
+            s = r.choice(stacks)
+            if self.push(s):
+                self.pop(s, d=self.lo[s] if r.random() < 0.7 else None)
+            return
+        for _ in range(r.randint(2, 3)):
+            s = r.choice(stacks)
+            if self.lo[s] == 0 or r.random() < 0.45:
+                if not self.push(s):
+                    self.pop(s)
+            else:
+                self.pop(s)
+
+    def branch(self, stacks, level):
+        """A branch on the input (stashed in the node's own R1): the arms use
+        the stacks in different orders and to different depths.  ``level``:
+        both arms pop down to common depths before they join."""
+        r = self.r
+        a1, j = self.label(), self.label()
+        self.lines += ["MOV R1, ACC", f"{r.choice(['JGZ', 'JLZ', 'JEZ'])} {a1}"]
+        hi0, lo0 = dict(self.hi), dict(self.lo)
+        order = list(stacks)
+        r.shuffle(order)
+        ends = []
+        for arm in range(2):
+            self.hi, self.lo = dict(hi0), dict(lo0)
+            if arm:
+                self.lines += [f"JMP {j}", f"{a1}: NOP"]
+                order = order[::-1]
+            for s in order[:r.randint(1, len(order))]:
+                if self.lo[s] and r.random() < 0.4:
+                    self.pop(s)
+                elif self.push(s) and r.random() < 0.5:
+                    self.pop(s)
+            ends.append((len(self.lines), dict(self.hi)))
+        if level:
+            low = {s: min(e[1][s] for e in ends) for s in self.hi}
+            tail = self.lines[ends[0][0]:]
+            del self.lines[ends[0][0]:]
+            for e, rest in ((ends[0], tail), (ends[1], [])):
+                self.hi, self.lo = dict(e[1]), dict(e[1])
+                for s in stacks:
+                    if self.hi[s] > low[s]:
+                        self.pop(s, d=self.hi[s] - low[s])
+                self.lines += rest
+            self.hi, self.lo = dict(low), dict(low)
+        else:
+            self.hi = {s: max(e[1][s] for e in ends) for s in hi0}
+            self.lo = {s: min(e[1][s] for e in ends) for s in hi0}
+        self.lines.append(f"{j}: NOP")
+
+
+def _deep_stack(seed: int, session: bool, big: bool):
+    """(rows, deepest depth of each stack) of deep_stack_network."""
+    r = random.Random(0x5EED0000 + 4 * seed + 2 * bool(session) + bool(big))
+    ns = r.randint(3, 4) if big else r.randint(2, 4)
+    stacks = [f"s{k}" for k in range(ns)]
+    depths = DEEP_DEPTHS + (DEEP_BIG_DEPTHS if big else ())
+    g = _DeepGen(r, "a", stacks, 200 if big else 130, depths)
+    two = not session and r.random() < 0.34
+    branch = r.random() < 0.5
+    nseg = r.randint(2, 3) if session else 1
+    branch_seg = r.randrange(nseg) if branch else -1
+    rows = []
+    for seg in range(nseg):
+        g.lines += ["IN ACC", "SAV"]
+        if seg == branch_seg:
+            g.lines.append("MOV ACC, a:R1")  # the input, for the branch
+        mine = stacks
+        if two:
+            d0 = r.choice([x for x in depths if x >= 24])
+            g.push("s0", d=d0)
+            g.lines += ["SWP", "MOV ACC, b:R0", "SWP"]
+            b = _DeepGen(r, "b", ["s0", "t0"], g.limit, depths)
+            b.lines += ["MOV R0, ACC", "SAV"]
+            b.lo["s0"] = b.hi["s0"] = d0
+            b.pop("s0", nil=False)
+            if r.random() < 0.5:
+                b.push("t0")
+                b.pop("t0", d=b.lo["t0"], nil=False)
+                rows.append(("t0", "stack", ""))
+            b.lines += ["SWP", "MOV ACC, a:R0"]
+            g.peak["t0"] = b.peak["t0"]
+            rows.append(("b", "program", "\n".join(b.lines)))
+            g.lo["s0"] = g.hi["s0"] = b.lo["s0"]
+            mine = stacks[1:]
+        for _ in range(r.randint(1, 2) if session or two else r.randint(1, 3)):
+            g.block(mine)
+        if two:  # b's fold joins the running value
+            g.lines += ["SWP", "ADD R0", "SAV"]
+        if seg == branch_seg:
+            g.branch(stacks, level=session)
+        for _ in range(r.randint(1, 2)):
+            g.block(stacks)
+        last = seg == nseg - 1
+        for s in stacks:
+            if g.lo[s] and (session and last or not session and r.random() < 0.5):
+                g.pop(s, d=g.lo[s], nil=False if session else None)
+        g.lines += ["SWP", "OUT ACC"]
+    rows.append(("a", "program", "\n".join(g.lines)))
+    rows += [(s, "stack", "") for s in stacks]
+    r.shuffle(rows)
+    names = {row[0] for row in rows}
+    return rows, {s: d for s, d in g.peak.items() if s in names}
+
+
+def deep_stack_network(seed: int, *, session: bool = False, big: bool = False):
+    """Networks whose stack depths the schedule compiler knows (every trip
+    count is a constant), deep enough to spill to numbered slots: 2-4 stacks,
+    push runs (PUSH ACC with small and wide steps, PUSH imm) and pop runs
+    (folded in order, to NIL, partial) of lengths around every threshold
+    (DEEP_DEPTHS), in blocks that use the stacks one after the other, nested,
+    interleaved and half-drained, so that some stacks may share slots and
+    others interfere; about half the seeds branch on the input (JGZ / JLZ /
+    JEZ) into arms that use the stacks in different orders and to different
+    depths, and stacks may stay non-empty.  About a third are two nodes: ``a``
+    fills s0 and signals ``b``, which pops it (and may use a stack of its
+    own) while ``a`` works on other stacks, then hands its fold back and ends
+    blocked on a read.
+
+    ``session``: one node cut into 2-3 calls by ``SWP / OUT ACC / IN ACC /
+    SAV``; stacks may stay filled across a call, and every stack is drained
+    before the program wraps.  ``big``: depths up to 200.
+
+    Returns the rows.  Seeds 0..59 are pinned by digest
+    (test_jit_codegen.py test_deep_stack_network_rows_are_pinned)."""
+    return _deep_stack(seed, session, big)[0]
+
+
+def deep_stack_peaks(seed: int, *, session: bool = False, big: bool = False) -> dict:
+    """{stack: its deepest depth on any path} of deep_stack_network(seed)."""
+    return _deep_stack(seed, session, big)[1]
+
+
+def deep_seed_kwargs(seed: int) -> dict:
+    """Budget and capacity of a seeded deep-stack case: budgets that end lanes
+    inside runs, capacities at and around the register-resident entries."""
+    kw = dict(budget=[None, 300, 1000, 2500][seed % 4], stack_cap=[None, 24, 64, 100][seed // 4 % 4])
+    return {k: v for k, v in kw.items() if v is not None}
+
+
+def deep_stack_inputs(seed: int, n: int = 613):
+    """gen_inputs(seed + 5, n) with every seventh input 0: each wave mixes the
+    three sign classes of the branch."""
+    from oracle import pyoracle as po
+
+    xs = po.gen_inputs(seed + 5, n)
+    xs[::7] = 0
+    return xs
 
 
 # ---- stack loops that count before they push ----------------------------------
