@@ -329,6 +329,79 @@ int mk_session_reset_indexed(mk_session *s, const uint32_t *sel, size_t m);
  * session.  Synchronous. */
 int mk_session_call_open(mk_session *s, const uint32_t *sel, size_t m, uint8_t *open);
 
+/* ---- snapshots: a session's state out of the set and back -------------------
+ * A session record is one session's whole state -- registers, ports, pending
+ * sends, stacks, inChan / outChan, its open call, the tier that holds it --
+ * as layout.rows 32-bit rows; an int64 takes two rows, low word first.  A
+ * block of m records is laid out [row][m]: row r of entry t is rec[r*m + t].
+ *   control    held io csteps pin in_val out_val bits pfull(2)
+ *   per program node, sorted-name order
+ *              acc(2) bak(2) ip pendv port[4]
+ *   per stack  depth, then stack_cap entries (0 at and above the depth)
+ *   native     sb, registers (2 rows each), stack slots: layout.native_rows
+ *              rows, present only in blocks of a native-tier set, all zero for
+ *              a record with held == 0
+ * held: 1 when the native tier held the session, 0 when the interpreter did.
+ * io: in_full | out_full << 1 | input not deposited << 2 | call open << 3 |
+ * ended (MK_ST_STACK_OVERFLOW) << 4.  bits: pend | hung << 16, one bit per
+ * program node.  Everything but the native section is the CANONICAL part, in
+ * the bytecode interpreter's terms and always filled: a session the native
+ * tier holds is between calls, so its record has the call closed.  The
+ * canonical part of one history need not be word-identical between tiers (the
+ * compiler drops dead values, the interpreter keeps stale ones in empty
+ * ports); restored, it behaves identically.
+ *
+ * A restore overwrites the listed sessions completely.  A record with
+ * held == 1 goes back to the native tier when the block's native_hash is the
+ * set's own (and not 0); every other record is restored from its canonical
+ * part, and in a native-tier set that session is the interpreter's from then
+ * on, as after a hand-off.  So a block can go to another set, another GPU or
+ * another tier of the same network at the same stack_cap.
+ *
+ * Both operations are ordered against every other launch of the set like the
+ * indexed forms; MK_EDEVICE on a set broken by a failed launch; MK_EINVAL for
+ * sets of a network with remote peers (part of their state lives in the
+ * peers).  sel NULL with m == n: every session.  m == 0 is MK_OK and
+ * launches nothing. */
+typedef struct {
+    uint32_t magic;       /* "MKSR" */
+    uint32_t version;
+    uint64_t net_hash;    /* node names, kinds and the lowered bytecode */
+    uint64_t native_hash; /* the session module's generated source; 0: interpreter-tier set */
+    uint32_t nprog;
+    uint32_t nstack;
+    uint32_t stack_cap;
+    uint32_t rows;        /* of one record, the native section included */
+    uint32_t native_rows; /* 1 + 2 * registers + slots, or 0 */
+    uint32_t reserved;
+} mk_session_layout;
+
+int mk_session_layout_get(const mk_session *s, mk_session_layout *out);
+/* Host form, synchronous: rec is a host block [rows][m]; sel is checked as in
+ * the indexed forms.  Staged through a temporary device block in chunks of
+ * entries of at most 64 MiB of rows; MK_ENOMEM if one chunk cannot be had. */
+int mk_session_snapshot(mk_session *s, const uint32_t *sel, size_t m, uint32_t *rec);
+/* Device form, asynchronous on `stream`: d_sel as in
+ * mk_session_compute_indexed_device (an entry >= n gives an all-zero record). */
+int mk_session_snapshot_device(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t *d_rec, void *stream);
+/* Session sel[t] takes column col[t] (t with col NULL) of the block rec of
+ * mcols columns described by `from`.  MK_EINVAL before anything is queued
+ * when `from` disagrees with the set in magic, version, net_hash, nprog,
+ * nstack or stack_cap, or its rows are not those of its sections.  The host
+ * form also checks sel and every referenced record -- col[t] < mcols,
+ * held <= 1, every ip inside its node's program, every depth <= stack_cap,
+ * and for a record that goes back to the native tier an sb that is either
+ * "ended" or a superblock a call starts at -- and returns MK_EINVAL for the
+ * first bad one with no session changed. */
+int mk_session_restore(mk_session *s, const uint32_t *sel, size_t m, const mk_session_layout *from,
+                       const uint32_t *rec, size_t mcols, const uint32_t *col);
+/* Device form: d_sel, d_rec and d_col are taken ON TRUST and kept valid and
+ * unchanged until the launch completes.  The net below that contract is the
+ * kernel's own guard: an entry that fails one of the checks above restores
+ * nothing and leaves its session untouched. */
+int mk_session_restore_device(mk_session *s, const uint32_t *d_sel, size_t m, const mk_session_layout *from,
+                              const uint32_t *d_rec, size_t mcols, const uint32_t *d_col, void *stream);
+
 void mk_session_free(mk_session *s);
 
 /* Add the counters accumulated by MK_FLAG_DEFER_STATS launches on `device`

@@ -11,6 +11,7 @@ from .network import (
     Network,
     NodeSpec,
     SessionSet,
+    SessionSnapshot,
     TisParseError,
     generate_inputs_device,
     tokenize,
@@ -23,6 +24,7 @@ __all__ = [
     "Network",
     "NodeSpec",
     "SessionSet",
+    "SessionSnapshot",
     "TisParseError",
     "generate_inputs_device",
     "tokenize",

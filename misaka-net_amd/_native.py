@@ -93,6 +93,13 @@ class mk_input(C.Structure):
     ]
 
 
+class mk_session_layout(C.Structure):
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("net_hash", C.c_uint64),
+                ("native_hash", C.c_uint64), ("nprog", C.c_uint32), ("nstack", C.c_uint32),
+                ("stack_cap", C.c_uint32), ("rows", C.c_uint32), ("native_rows", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol include/mk.h declares.
 SIGNATURES = {
     "mk_net_load": (C.c_int, [C.POINTER(mk_node_desc), C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]),
@@ -133,6 +140,15 @@ SIGNATURES = {
     "mk_session_cancel_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mk_session_reset_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mk_session_call_open": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mk_session_layout_get": (C.c_int, [C.c_void_p, C.POINTER(mk_session_layout)]),
+    "mk_session_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mk_session_snapshot_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mk_session_restore": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(mk_session_layout), C.c_void_p, C.c_size_t,
+                  C.c_void_p]),
+    "mk_session_restore_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(mk_session_layout), C.c_void_p, C.c_size_t,
+                  C.c_void_p, C.c_void_p]),
     "mk_session_reset": (C.c_int, [C.c_void_p]),
     "mk_session_cancel": (C.c_int, [C.c_void_p]),
     "mk_session_plan": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),

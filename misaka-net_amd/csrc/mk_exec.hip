@@ -68,6 +68,7 @@ extern char **environ;
 #include "tis_sched.h"
 #define MK_HD __host__ __device__
 #include "sess_convert.h"
+#include "sess_record.h"
 
 namespace mk {
 
@@ -1466,6 +1467,178 @@ __global__ void __launch_bounds__(kBlock) tis_session_reset_sel(SessParams p, Se
     if (q.nsb) {
         if (q.nsb[i] == kSessT1) atomicSub(&q.sflags[1], 1u);
         q.nsb[i] = 0u;
+        q.hand_sb[i] = 0u;
+        q.hand_steps[i] = 0u;
+        q.hand_call[i] = 0u;
+    }
+}
+
+// ---- snapshots: a session's state out of the set and back (sess_record.h) ----
+// The native side of a set for the two kernels below (nsb null without the
+// native tier), and for a restore what it needs to know of the block.
+struct SessSnapK {
+    uint32_t *nsb, *hand_sb, *hand_steps, *hand_call, *sflags;
+    int64_t *regs;
+    int32_t *slots;
+    uint32_t nregs, nslots;
+    const SessMapHdr *hdr;
+    const SessSrcDev *map;
+    const int64_t *dyn_base;
+    const uint32_t *pre;      // bit k: a call starts at superblock k (its map has `pre`)
+    uint32_t nsbk;            // superblocks
+    uint32_t nat_ok;          // the block's native section is this set's own (native_hash agrees)
+};
+
+// mk_session_snapshot: thread t of m writes column t of the block rec
+// ([row][m]) from session sel[t] (first + t with sel null).  blockIdx.y 0
+// writes the canonical words -- for a session the native tier holds the whole
+// canonical part, converted through its superblock's state map; the tall row
+// groups that are plain copies (an interpreter session's stack entries, the
+// native registers and slots) are shared among the grid's y.  Reads state,
+// writes none.
+__global__ void __launch_bounds__(kBlock) tis_session_export_sel(SessParams p, SessSnapK q, const uint32_t *sel,
+                                                                 uint64_t first, uint64_t m, uint32_t *rec)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= m) return;
+    const uint64_t i = sel ? (uint64_t)sel[t] : first + t, n = p.n;
+    const SessRecShape L{p.nprog, p.nstack, p.stack_cap, q.nregs, q.nslots};
+    const uint32_t rows = L.canon_rows() + (q.nsb ? L.native_rows() : 0u);
+    auto put = [&](uint32_t r, uint32_t v) { rec[(uint64_t)r * m + t] = v; };
+    if (i >= n) { // names no session: an all-zero record
+        for (uint32_t r = blockIdx.y; r < rows; r += gridDim.y) put(r, 0u);
+        return;
+    }
+    const uint32_t sb = q.nsb ? q.nsb[i] : kSessT1;
+    const bool held = sb != kSessT1;
+    if (q.nsb) { // the native section: zero unless the native tier holds the session
+        for (uint32_t r = blockIdx.y; r < 2u * q.nregs; r += gridDim.y) {
+            const uint64_t v = held ? (uint64_t)q.regs[(uint64_t)(r >> 1) * n + i] : 0ull;
+            put(L.reg_row(0) + r, (uint32_t)(v >> (32u * (r & 1u))));
+        }
+        for (uint32_t r = blockIdx.y; r < q.nslots; r += gridDim.y)
+            put(L.slot_row(r), held ? (uint32_t)q.slots[(uint64_t)r * n + i] : 0u);
+    }
+    if (!held) {
+        const uint32_t srows = (uint32_t)p.nstack * p.stack_cap;
+        for (uint32_t r = blockIdx.y; r < srows; r += gridDim.y) {
+            const uint32_t s = r / p.stack_cap, j = r % p.stack_cap;
+            const uint32_t d = (uint32_t)p.sdepth[(uint64_t)s * n + i];
+            put(L.stack((int)s) + 1u + j, j < d ? (uint32_t)p.stk[(uint64_t)r * n + i] : 0u);
+        }
+    }
+    if (blockIdx.y) return;
+    if (q.nsb) put(L.sb_row(), held ? sb : 0u);
+    if (held && sb != kSessDead && sb / 2u >= q.nsbk) { // no session between launches is in such a state
+        for (uint32_t r = 0; r < L.canon_rows(); r++) put(r, r == SR_HELD ? 1u : 0u);
+        return;
+    }
+    if (held) {
+        auto reg = [&](uint32_t r) { return q.regs[(uint64_t)r * n + i]; };
+        auto slot = [&](uint32_t s) { return q.slots[(uint64_t)s * n + i]; };
+        sess_record_native(L, sb, q.hdr, q.map, q.dyn_base, reg, slot, put);
+        return;
+    }
+    put(SR_HELD, 0u);
+    put(SR_IO, p.io[i]);
+    put(SR_CSTEPS, p.csteps[i]);
+    put(SR_PIN, (uint32_t)p.pin[i]);
+    put(SR_IN_VAL, (uint32_t)p.in_val[i]);
+    put(SR_OUT_VAL, (uint32_t)p.out_val[i]);
+    put(SR_BITS, p.bits[i]);
+    const uint64_t pf = p.pfull[i];
+    put(SR_PFULL, (uint32_t)pf);
+    put(SR_PFULL + 1u, (uint32_t)(pf >> 32));
+    for (int k = 0; k < p.nprog; ++k) {
+        const uint64_t a = (uint64_t)p.acc[(uint64_t)k * n + i], b = (uint64_t)p.bak[(uint64_t)k * n + i];
+        const uint32_t r = L.node(k);
+        put(r + SR_ACC, (uint32_t)a);
+        put(r + SR_ACC + 1u, (uint32_t)(a >> 32));
+        put(r + SR_BAK, (uint32_t)b);
+        put(r + SR_BAK + 1u, (uint32_t)(b >> 32));
+        put(r + SR_IP, (uint32_t)p.ip[(uint64_t)k * n + i]);
+        put(r + SR_PENDV, (uint32_t)p.pendv[(uint64_t)k * n + i]);
+        for (int c = 0; c < 4; ++c) put(r + SR_PORT + c, (uint32_t)p.port[(uint64_t)(k * 4 + c) * n + i]);
+    }
+    for (int k = 0; k < p.nstack; ++k) put(L.stack(k), (uint32_t)p.sdepth[(uint64_t)k * n + i]);
+}
+
+// mk_session_restore: thread t of m overwrites session sel[t] (first + t with
+// sel null) completely with column col[t] (t with col null) of the block rec
+// ([row][mcols]).  A record the native tier held goes back to it when the
+// block's native section is this set's own (q.nat_ok): sb, registers and
+// slots are written and the interpreter's words zeroed (its stack entries,
+// dead above a depth of 0, stay).  Every other record
+// is restored from its canonical part into the interpreter's arrays, and in
+// a native-tier set the session is marked MK_SS_T1 -- the interpreter's from
+// then on, as a handed-off session is.  sflags[1] follows.  An entry whose
+// session, column or record is out of range (sess_record.h) restores nothing.
+// Every block of the grid's y reaches the same verdict from the record alone;
+// y 0 writes the session's words, the tall row groups are shared.
+__global__ void __launch_bounds__(kBlock) tis_session_restore_sel(SessParams p, SessSnapK q, const uint32_t *sel,
+                                                                  uint64_t first, uint64_t m, const uint32_t *rec,
+                                                                  uint64_t mcols, const uint32_t *col)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= m) return;
+    const uint64_t i = sel ? (uint64_t)sel[t] : first + t, n = p.n;
+    const uint64_t c = col ? (uint64_t)col[t] : t;
+    if (i >= n || c >= mcols) return;
+    // the block's shape: this set's canonical part (the host checked the layout), its own native section
+    const SessRecShape L{p.nprog, p.nstack, p.stack_cap, q.nregs, q.nslots};
+    auto get = [&](uint32_t r) { return rec[(uint64_t)r * mcols + c]; };
+    const bool native = get(SR_HELD) == 1u && q.nsb && q.nat_ok;
+    // a native restore's only tall rows are the registers and the slots: the rest of the grid's y
+    // has nothing to write, whatever the verdict
+    if (native && blockIdx.y >= q.nregs && blockIdx.y >= q.nslots && blockIdx.y) return;
+    if (!sess_record_ok(L, p.len, get)) return;
+    if (native && !sess_record_native_ok(L, q.nsbk, q.pre, q.hdr, q.map, q.dyn_base, get)) return;
+    // stack entries below the depth only: the rest are dead words (nothing reads an entry at or
+    // above its stack's depth, and a snapshot writes them as 0), and with a list these are 4-byte
+    // writes a cache line apart -- all stack_cap rows of them had cost 1.77 ms for 65,536 sessions
+    // of the example network (profiles/sessions_snapshot_probe.jsonl).  A native restore leaves
+    // the depths 0 and so writes none.
+    const uint32_t srows = native ? 0u : (uint32_t)p.nstack * p.stack_cap;
+    for (uint32_t r = blockIdx.y; r < srows; r += gridDim.y) {
+        const uint32_t s = r / p.stack_cap, j = r % p.stack_cap;
+        if (j < get(L.stack((int)s))) p.stk[(uint64_t)r * n + i] = (int32_t)get(L.stack((int)s) + 1u + j);
+    }
+    if (q.nsb) {
+        for (uint32_t r = blockIdx.y; r < q.nregs; r += gridDim.y)
+            q.regs[(uint64_t)r * n + i] =
+                native ? (int64_t)((uint64_t)get(L.reg_row(r)) | (uint64_t)get(L.reg_row(r) + 1u) << 32) : 0;
+        for (uint32_t r = blockIdx.y; r < q.nslots; r += gridDim.y)
+            q.slots[(uint64_t)r * n + i] = native ? (int32_t)get(L.slot_row(r)) : 0;
+    }
+    if (blockIdx.y) return;
+    for (int k = 0; k < p.nprog; ++k) {
+        const uint32_t r = L.node(k);
+        p.acc[(uint64_t)k * n + i] =
+            native ? 0 : (int64_t)((uint64_t)get(r + SR_ACC) | (uint64_t)get(r + SR_ACC + 1u) << 32);
+        p.bak[(uint64_t)k * n + i] =
+            native ? 0 : (int64_t)((uint64_t)get(r + SR_BAK) | (uint64_t)get(r + SR_BAK + 1u) << 32);
+        p.ip[(uint64_t)k * n + i] = native ? 0 : (int32_t)get(r + SR_IP);
+        p.pendv[(uint64_t)k * n + i] = native ? 0 : (int32_t)get(r + SR_PENDV);
+        p.xst[(uint64_t)k * n + i] = 0u;
+        p.xval[(uint64_t)k * n + i] = 0;
+        for (int d = 0; d < 4; ++d)
+            p.port[(uint64_t)(k * 4 + d) * n + i] = native ? 0 : (int32_t)get(r + SR_PORT + d);
+    }
+    for (int k = 0; k < p.nstack; ++k) p.sdepth[(uint64_t)k * n + i] = native ? 0 : (int32_t)get(L.stack(k));
+    p.pfull[i] = native ? 0ull : (uint64_t)get(SR_PFULL) | (uint64_t)get(SR_PFULL + 1u) << 32;
+    p.bits[i] = native ? 0u : get(SR_BITS);
+    // in_full, out_full, the open call (bits 2-3) and the dead field; the
+    // hand-off bits (8-14) belong to a launch, never to a record
+    p.io[i] = native ? 0u : get(SR_IO) & 0xFFu;
+    p.in_val[i] = native ? 0 : (int32_t)get(SR_IN_VAL);
+    p.out_val[i] = native ? 0 : (int32_t)get(SR_OUT_VAL);
+    p.pin[i] = native ? 0 : (int32_t)get(SR_PIN);
+    p.csteps[i] = native ? 0u : get(SR_CSTEPS);
+    if (q.nsb) {
+        const bool was = q.nsb[i] == kSessT1;
+        if (was && native) atomicSub(&q.sflags[1], 1u);
+        if (!was && !native) atomicAdd(&q.sflags[1], 1u);
+        q.nsb[i] = native ? get(L.sb_row()) : kSessT1;
         q.hand_sb[i] = 0u;
         q.hand_steps[i] = 0u;
         q.hand_call[i] = 0u;
@@ -3482,6 +3655,19 @@ struct mk_session {
     mk::SessMapHdr *hdr = nullptr;
     mk::SessSrcDev *rec = nullptr;
     int64_t *dyn_base = nullptr;
+    // snapshots (sess_record.h): what identifies a block as this set's, the
+    // superblocks a call starts at (device bitmap and host copy), and host
+    // copies of the maps for the host form's record checks
+    uint64_t net_hash = 0, native_hash = 0;
+    uint32_t *pre = nullptr;
+    uint32_t nsbk = 0;
+    std::vector<uint32_t> h_pre;
+    std::vector<mk::SessMapHdr> h_hdr;
+    std::vector<mk::SessSrcDev> h_rec;
+    std::vector<int64_t> h_dyn_base;
+    // a restore may have given the interpreter sessions of a set whose calls
+    // never hand off: its pass is then launched all the same
+    bool interp_may_hold = false;
     ~mk_session()
     {
         mk::DeviceGuard g(device);
@@ -3561,7 +3747,7 @@ int session_launch(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *
         void *kargs[] = {d_sel ? (void *)&ks : (void *)&k};
         // the native kernel is the launch's last when the interpreter pass is
         // skipped (below: no call can reach the budget)
-        const bool last = s->call_steps < (uint64_t)p.budget;
+        const bool last = s->call_steps < (uint64_t)p.budget && !s->interp_may_hold;
         if (hipExtModuleLaunchKernel(d_sel ? s->fn_sel : s->fn, (uint32_t)(blocks * kBlock), 1, 1, kBlock, 1, 1, 0,
                                      stream, kargs, nullptr, nullptr, last ? done : nullptr, 0) != hipSuccess)
             return MK_EDEVICE;
@@ -3573,7 +3759,7 @@ int session_launch(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *
                            s->regs, s->slots, s->hdr, s->rec, s->dyn_base};
         // no call of this network can reach the budget: none hands off and
         // the interpreter holds no session, so its pass would only exit
-        if (s->call_steps < (uint64_t)p.budget) return MK_OK;
+        if (last) return MK_OK;
     }
     // 3. the interpreter: its sessions (all of them without the native tier)
     void *args[] = {(void *)&code, (void *)&p};
@@ -3626,7 +3812,8 @@ int session_native(mk_session *s)
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t sz[] = {al(N * 4), al((size_t)P.nregs * N * 8), al((size_t)std::max<uint32_t>(P.nslots, 1) * N * 4),
                          al(N * 4), al(N * 4), al(N * 4), al(16), al(hdr.size() * sizeof(SessMapHdr)),
-                         al(rec.size() * sizeof(SessSrcDev)), al(std::max<size_t>(P.dyn_base.size(), 1) * 8)};
+                         al(rec.size() * sizeof(SessSrcDev)), al(std::max<size_t>(P.dyn_base.size(), 1) * 8),
+                         al((hdr.size() + 31) / 32 * 4 + 4)};
     size_t total = 0;
     for (size_t b : sz) total += b;
     if (hipMalloc(&s->d_native, total) != hipSuccess) return MK_ENOMEM;
@@ -3644,6 +3831,12 @@ int session_native(mk_session *s)
     s->hdr = (SessMapHdr *)take(7);
     s->rec = (SessSrcDev *)take(8);
     s->dyn_base = (int64_t *)take(9);
+    s->pre = (uint32_t *)take(10);
+    s->nsbk = (uint32_t)hdr.size();
+    s->h_pre.assign((hdr.size() + 31) / 32 + 1, 0u);
+    for (size_t k = 0; k < hdr.size(); k++)
+        if (hdr[k].flags & 16u) s->h_pre[k >> 5] |= 1u << (k & 31);
+    s->native_hash = src_hash(src);
     s->nregs = P.nregs;
     s->nslots = std::max<uint32_t>(P.nslots, 1);
     // the maps never change: copied once (reset clears only the lane state)
@@ -3652,8 +3845,12 @@ int session_native(mk_session *s)
         (!rec.empty() && hipMemcpy(s->rec, rec.data(), rec.size() * sizeof(SessSrcDev), hipMemcpyHostToDevice) !=
                              hipSuccess) ||
         (!P.dyn_base.empty() &&
-         hipMemcpy(s->dyn_base, P.dyn_base.data(), P.dyn_base.size() * 8, hipMemcpyHostToDevice) != hipSuccess))
+         hipMemcpy(s->dyn_base, P.dyn_base.data(), P.dyn_base.size() * 8, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(s->pre, s->h_pre.data(), s->h_pre.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
         return MK_EDEVICE;
+    s->h_hdr = std::move(hdr);
+    s->h_rec = std::move(rec);
+    s->h_dyn_base = P.dyn_base;
     s->native_bytes = sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + sz[5] + sz[6]; // the lane state: what a reset clears
     s->native = true;
     s->call_steps = jit_session_max_call_steps(P, h->jit_lim);
@@ -3843,6 +4040,14 @@ int mk_compute_device(mk_net *h, int device, const mk_input *in, size_t n, int32
     return mk::launch_locked(h, device, in, n, d_out, d_status, d_steps, d_stats, opts, (hipStream_t)stream);
 }
 
+extern "C++" {
+namespace mk {
+namespace {
+uint64_t net_hash(const Network &N);
+}
+} // namespace mk
+}
+
 int mk_session_create(mk_net *h, int device, size_t n, const mk_opts *opts, mk_session **out)
 {
     if (!h || !out) return MK_EINVAL;
@@ -3864,6 +4069,7 @@ int mk_session_create(mk_net *h, int device, size_t n, const mk_opts *opts, mk_s
         int rc = mk::ensure_device(h, device);
         if (rc) return rc;
         s->nprog = h->net.nprog;
+        s->net_hash = mk::net_hash(h->net);
         // remote peers of a mixed deployment may push to / pop from local stacks
         s->nstack = h->net.uses_stacks || h->net.uses_remote ? h->net.nstack : 0;
     }
@@ -3954,6 +4160,7 @@ int mk_session_reset(mk_session *s)
     if (s->native && hipMemsetAsync(s->d_native, 0, s->native_bytes, s->stream) != hipSuccess) return MK_EDEVICE;
     if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
     s->broken = false; // every session back to its initial state, none handed off
+    s->interp_may_hold = false;
     return MK_OK;
 }
 
@@ -4461,6 +4668,261 @@ int mk_session_call_open(mk_session *s, const uint32_t *sel, size_t m, uint8_t *
         hipStreamSynchronize(s->stream) != hipSuccess)
         return MK_EDEVICE;
     memcpy(open, (char *)s->h_stage + o_open, m);
+    return MK_OK;
+}
+
+// ---- snapshots: session records out of a set and back (sess_record.h) --------
+extern "C++" {
+namespace mk {
+namespace {
+// What identifies a network to a record: FNV-1a over the node names, their
+// kinds and the lowered bytecode.
+uint64_t net_hash(const Network &N)
+{
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&](const void *p, size_t k) {
+        for (size_t i = 0; i < k; i++) h = (h ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
+    };
+    auto str = [&](const std::string &x, int kind) {
+        mix(x.c_str(), x.size() + 1);
+        mix(&kind, sizeof kind);
+    };
+    for (const std::string &x : N.prog_names) str(x, NK_PROGRAM);
+    for (const std::string &x : N.stack_names) str(x, NK_STACK);
+    for (size_t i = 0; i < N.remote_names.size(); i++) str(N.remote_names[i], N.remote_kinds[i]);
+    for (size_t k = 0; k < N.base.size(); k++) {
+        mix(&N.base[k], 4);
+        mix(&N.len[k], 4);
+    }
+    for (const Insn &I : N.code) {
+        const int64_t w[6] = {I.op, I.src, I.dst, I.arg, I.imm, 0};
+        mix(w, sizeof w);
+    }
+    return h;
+}
+
+SessRecShape session_shape(const mk_session *s) { return SessRecShape{s->nprog, s->nstack, s->cap, s->nregs, s->nslots}; }
+
+void session_layout(const mk_session *s, mk_session_layout *out)
+{
+    const SessRecShape L = session_shape(s);
+    *out = mk_session_layout{};
+    out->magic = kSessRecMagic;
+    out->version = kSessRecVersion;
+    out->net_hash = s->net_hash;
+    out->native_hash = s->native ? s->native_hash : 0;
+    out->nprog = (uint32_t)s->nprog;
+    out->nstack = (uint32_t)s->nstack;
+    out->stack_cap = s->cap;
+    out->native_rows = s->native ? L.native_rows() : 0u;
+    out->rows = L.canon_rows() + out->native_rows;
+}
+
+// A block's layout against the set's: the canonical part must be this
+// network's at this stack_cap, the block's row count its own sections'.
+bool layout_fits(const mk_session *s, const mk_session_layout *from)
+{
+    mk_session_layout own;
+    session_layout(s, &own);
+    return from->magic == own.magic && from->version == own.version && from->net_hash == own.net_hash &&
+           from->nprog == own.nprog && from->nstack == own.nstack && from->stack_cap == own.stack_cap &&
+           from->rows == own.rows - own.native_rows + from->native_rows && from->rows >= from->native_rows;
+}
+
+// the block's native section is this set's own
+bool layout_native(const mk_session *s, const mk_session_layout *from)
+{
+    return s->native && from->native_hash != 0 && from->native_hash == s->native_hash &&
+           from->native_rows == session_shape(s).native_rows();
+}
+
+SessSnapK session_snapk(const mk_session *s, bool nat_ok)
+{
+    SessSnapK q{};
+    if (s->native)
+        q = SessSnapK{s->nsb, s->hand_sb, s->hand_steps, s->hand_call, s->sflags, s->regs, s->slots, s->nregs,
+                      s->nslots, s->hdr, s->rec, s->dyn_base, s->pre, s->nsbk, nat_ok ? 1u : 0u};
+    return q;
+}
+
+// Grid of the two kernels: one thread per entry, the tall row groups over y.
+dim3 snap_grid(const mk_session *s, unsigned blocks)
+{
+    const uint64_t tall = std::max<uint64_t>(
+        {(uint64_t)s->nstack * s->cap, s->native ? 2ull * s->nregs : 0ull, s->native ? (uint64_t)s->nslots : 0ull, 1ull});
+    return dim3(blocks, (unsigned)std::min<uint64_t>(tall, 64));
+}
+
+// Queues the export of m entries (sessions d_sel[t], or first + t) into the
+// device block d_rec on `st`; `done` as in session_launch.
+int snapshot_launch(mk_session *s, const uint32_t *d_sel, uint64_t first, uint64_t m, uint32_t *d_rec, hipStream_t st,
+                    hipEvent_t done)
+{
+    unsigned blocks;
+    if (!sel_grid(m, &blocks)) return MK_ELIMIT;
+    SessParams p = s->p;
+    SessSnapK q = session_snapk(s, false);
+    void *args[] = {(void *)&p, (void *)&q, (void *)&d_sel, (void *)&first, (void *)&m, (void *)&d_rec};
+    return hipExtLaunchKernel(reinterpret_cast<void *>(&tis_session_export_sel), snap_grid(s, blocks), dim3(kBlock), args,
+                              0, st, nullptr, done, 0) == hipSuccess
+               ? MK_OK
+               : MK_EDEVICE;
+}
+
+// may_hold: a record of the block may be restored from its canonical part.
+int restore_launch(mk_session *s, const uint32_t *d_sel, uint64_t first, uint64_t m, bool nat_ok, bool may_hold,
+                   const uint32_t *d_rec, uint64_t mcols, const uint32_t *d_col, hipStream_t st, hipEvent_t done)
+{
+    unsigned blocks;
+    if (!sel_grid(m, &blocks)) return MK_ELIMIT;
+    SessParams p = s->p;
+    SessSnapK q = session_snapk(s, nat_ok);
+    void *args[] = {(void *)&p,     (void *)&q,     (void *)&d_sel, (void *)&first,
+                    (void *)&m,     (void *)&d_rec, (void *)&mcols, (void *)&d_col};
+    if (hipExtLaunchKernel(reinterpret_cast<void *>(&tis_session_restore_sel), snap_grid(s, blocks), dim3(kBlock), args,
+                           0, st, nullptr, done, 0) != hipSuccess)
+        return MK_EDEVICE;
+    if (may_hold) s->interp_may_hold = true; // a canonical restore hands its session to the interpreter
+    return MK_OK;
+}
+
+// Entries of a host form's staging chunk: at most 64 MiB of rows.
+size_t snap_chunk(uint32_t rows, size_t m) { return std::min<size_t>(m, std::max<size_t>(1, ((size_t)64 << 20) / ((size_t)rows * 4))); }
+
+struct DevBlock {
+    void *p = nullptr;
+    ~DevBlock() { (void)hipFree(p); }
+};
+} // namespace
+} // namespace mk
+}
+
+int mk_session_layout_get(const mk_session *s, mk_session_layout *out)
+{
+    if (!s || !out) return MK_EINVAL;
+    if (s->p.mixed) return MK_EINVAL; // part of the state lives in the peers
+    mk::session_layout(s, out);
+    return MK_OK;
+}
+
+int mk_session_snapshot(mk_session *s, const uint32_t *sel, size_t m, uint32_t *rec)
+{
+    if (!s || (m && !rec)) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->p.mixed) return MK_EINVAL;
+    if (sel ? !mk::sel_valid(s, sel, m) : m != s->n) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (m == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    mk_session_layout lay;
+    mk::session_layout(s, &lay);
+    const size_t chunk = mk::snap_chunk(lay.rows, m);
+    mk::DevBlock blk;
+    if (hipMalloc(&blk.p, (size_t)lay.rows * chunk * 4) != hipSuccess) return MK_ENOMEM;
+    uint32_t *d_sel;
+    if (int rc = mk::session_stage_sel(s, sel, m, 0, &d_sel)) return rc;
+    for (size_t t0 = 0; t0 < m; t0 += chunk) {
+        const size_t c = std::min(chunk, m - t0);
+        if (int rc = mk::snapshot_launch(s, d_sel ? d_sel + t0 : nullptr, t0, c, (uint32_t *)blk.p, s->stream, nullptr))
+            return rc;
+        // column t0 .. t0 + c of the caller's [row][m] block
+        if (hipMemcpy2DAsync(rec + t0, m * 4, blk.p, c * 4, c * 4, lay.rows, hipMemcpyDeviceToHost, s->stream) !=
+                hipSuccess ||
+            hipStreamSynchronize(s->stream) != hipSuccess)
+            return MK_EDEVICE;
+    }
+    return MK_OK;
+}
+
+int mk_session_snapshot_device(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t *d_rec, void *stream)
+{
+    if (!s || (m && !d_rec)) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->p.mixed || m > s->n || (!d_sel && m != s->n)) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (m == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    // ordered against every other launch of the set (mk_session_compute_seq_device)
+    if (int rc = mk::session_wait_last(s, st)) return rc;
+    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
+    if (int rc = mk::snapshot_launch(s, d_sel, 0, m, d_rec, st, s->order)) return rc;
+    s->last = st;
+    return MK_OK;
+}
+
+int mk_session_restore(mk_session *s, const uint32_t *sel, size_t m, const mk_session_layout *from,
+                       const uint32_t *rec, size_t mcols, const uint32_t *col)
+{
+    if (!s || !from || (m && !rec)) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->p.mixed || !mk::layout_fits(s, from)) return MK_EINVAL;
+    if (sel ? !mk::sel_valid(s, sel, m) : m != s->n) return MK_EINVAL;
+    if (!col && m > mcols) return MK_EINVAL;
+    const bool nat_ok = mk::layout_native(s, from);
+    // every referenced record, with the kernel's own checks: nothing is queued for a bad block
+    mk::SessRecShape L = mk::session_shape(s);
+    bool may_hold = false;
+    for (size_t t = 0; t < m; t++) {
+        const size_t c = col ? col[t] : t;
+        if (c >= mcols) return MK_EINVAL;
+        auto get = [&](uint32_t r) { return rec[(size_t)r * mcols + c]; };
+        if (!mk::sess_record_ok(L, s->p.len, get)) return MK_EINVAL;
+        if (get(mk::SR_HELD) == 1u && nat_ok &&
+            !mk::sess_record_native_ok(L, s->nsbk, s->h_pre.data(), s->h_hdr.data(), s->h_rec.data(),
+                                       s->h_dyn_base.data(), get))
+            return MK_EINVAL;
+        may_hold |= !(get(mk::SR_HELD) == 1u && nat_ok);
+    }
+    if (s->broken) return MK_EDEVICE;
+    if (m == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    const size_t chunk = mk::snap_chunk(from->rows, m);
+    mk::DevBlock blk;
+    if (hipMalloc(&blk.p, (size_t)from->rows * chunk * 4) != hipSuccess) return MK_ENOMEM;
+    std::vector<uint32_t> host;
+    try {
+        host.resize((size_t)from->rows * chunk);
+    } catch (const std::bad_alloc &) {
+        return MK_ENOMEM;
+    }
+    uint32_t *d_sel;
+    if (int rc = mk::session_stage_sel(s, sel, m, 0, &d_sel)) return rc;
+    for (size_t t0 = 0; t0 < m; t0 += chunk) {
+        const size_t c = std::min(chunk, m - t0);
+        // the chunk's records gathered into a dense [row][c] block: entry j takes its column j
+        for (size_t r = 0; r < from->rows; r++)
+            for (size_t j = 0; j < c; j++) host[r * c + j] = rec[r * mcols + (col ? col[t0 + j] : t0 + j)];
+        if (hipMemcpyAsync(blk.p, host.data(), (size_t)from->rows * c * 4, hipMemcpyHostToDevice, s->stream) !=
+            hipSuccess)
+            return MK_EDEVICE;
+        if (int rc = mk::restore_launch(s, d_sel ? d_sel + t0 : nullptr, t0, c, nat_ok, may_hold, (const uint32_t *)blk.p, c,
+                                        nullptr, s->stream, nullptr))
+            return rc;
+        if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
+    }
+    return MK_OK;
+}
+
+int mk_session_restore_device(mk_session *s, const uint32_t *d_sel, size_t m, const mk_session_layout *from,
+                              const uint32_t *d_rec, size_t mcols, const uint32_t *d_col, void *stream)
+{
+    if (!s || !from || (m && !d_rec)) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->p.mixed || !mk::layout_fits(s, from)) return MK_EINVAL;
+    if (m > s->n || (!d_sel && m != s->n) || (!d_col && m > mcols)) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (m == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    if (int rc = mk::session_wait_last(s, st)) return rc;
+    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
+    if (int rc = mk::restore_launch(s, d_sel, 0, m, mk::layout_native(s, from), true, d_rec, mcols, d_col, st,
+                                    s->order))
+        return rc;
+    s->last = st;
     return MK_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "tis_jit.h"
 #include "tis_sched.h"
 #include "sess_convert.h"
+#include "sess_record.h"
 
 namespace {
 
@@ -415,6 +416,77 @@ int mkc_sess_export(void *ev, size_t i, orc_flat *f, int32_t *entries)
     f->entries = entries;
     f->csteps = e->hand_steps[i];
     return bad ? -3 : 0;
+}
+
+// Session i between calls (live, not handed off), as mk_session_snapshot gives
+// it: its canonical record (sess_record.h sess_record_native over the map of
+// the superblock its next call starts at, the call closed) written into one
+// column and read back into the oracle's terms.  entries: [stack][cap].
+int mkc_sess_export_idle(void *ev, size_t i, orc_flat *f, int32_t *entries)
+{
+    auto *e = (SessEmu *)ev;
+    if (i >= e->sb.size() || e->state[i] != 0) return -1;
+    if ((e->sb[i] & 1u) || e->sb[i] / 2 >= e->hdr.size()) return -2;
+    if (!(e->hdr[e->sb[i] / 2].flags & 16u)) return -4; // not a superblock a call starts at
+    const mk::SessRecShape L{e->N, e->S, e->cap, e->P.nregs, e->P.nslots};
+    std::vector<uint32_t> rec(L.canon_rows(), 0xA5A5A5A5u); // every row must be written
+    std::vector<uint8_t> put_once(L.canon_rows(), 0);
+    bool bad = false;
+    auto reg = [&](uint32_t r) { return e->R[i].at(r); };
+    auto slot = [&](uint32_t s) -> int32_t {
+        auto it = e->slots[i].find(s);
+        if (it == e->slots[i].end()) { bad = true; return 0; }
+        return it->second;
+    };
+    auto put = [&](uint32_t r, uint32_t v) { rec.at(r) = v; put_once[r] = 1; };
+    mk::sess_record_native(L, e->sb[i], e->hdr.data(), e->rec.data(), e->P.dyn_base.data(), reg, slot, put);
+    for (uint8_t w : put_once)
+        if (!w) return -5;
+    auto get = [&](uint32_t r) { return rec[r]; };
+    std::vector<uint32_t> len(e->N, UINT32_MAX);
+    if (!mk::sess_record_ok(L, len.data(), get) || get(mk::SR_HELD) != 1u) return -6;
+    memset(f, 0, sizeof *f);
+    auto g64 = [&](uint32_t r) { return (int64_t)((uint64_t)get(r) | (uint64_t)get(r + 1) << 32); };
+    for (int n = 0; n < e->N; n++) {
+        const uint32_t r = L.node(n);
+        f->acc[n] = g64(r + mk::SR_ACC);
+        f->bak[n] = g64(r + mk::SR_BAK);
+        f->ip[n] = (int32_t)get(r + mk::SR_IP);
+        f->pendv[n] = (int32_t)get(r + mk::SR_PENDV);
+        for (int k = 0; k < 4; k++) f->port[4 * n + k] = (int32_t)get(r + mk::SR_PORT + k);
+    }
+    f->pfull = (uint64_t)g64(mk::SR_PFULL);
+    f->pend = get(mk::SR_BITS) & 0xffffu;
+    f->hung = get(mk::SR_BITS) >> 16;
+    const uint32_t io = get(mk::SR_IO);
+    if (io & ~3u) return -7; // the call closed, the session live
+    f->in_full = io & 1u;
+    f->out_full = (io >> 1) & 1u;
+    f->in_val = (int32_t)get(mk::SR_IN_VAL);
+    f->out_val = (int32_t)get(mk::SR_OUT_VAL);
+    for (int s = 0; s < e->S; s++) {
+        f->depth[s] = get(L.stack(s));
+        for (uint32_t d = 0; d < e->cap; d++) entries[(size_t)s * e->cap + d] = (int32_t)get(L.stack(s) + 1 + d);
+    }
+    f->entries = entries;
+    f->pin = (int32_t)get(mk::SR_PIN);
+    f->csteps = get(mk::SR_CSTEPS);
+    return bad ? -3 : 0;
+}
+
+// Session dst becomes a copy of session src: the native raw path of a restore.
+int mkc_sess_copy(void *ev, size_t dst, size_t src)
+{
+    auto *e = (SessEmu *)ev;
+    if (dst >= e->sb.size() || src >= e->sb.size()) return -1;
+    if (dst == src) return 0;
+    e->sb[dst] = e->sb[src];
+    e->R[dst] = e->R[src];
+    e->slots[dst] = e->slots[src];
+    e->state[dst] = e->state[src];
+    e->hand_sb[dst] = e->hand_sb[src];
+    e->hand_steps[dst] = e->hand_steps[src];
+    return 0;
 }
 
 // The session lane of the native tier (tis_jit.h jit_session_lane) for the

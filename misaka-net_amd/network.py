@@ -487,6 +487,101 @@ class SessionSet:
             return
         N.check(N.lib().mk_session_reset(self._h), "mk_session_reset")
 
+    # ---- snapshots (include/mk.h: a session's state out of the set and back) ----
+    def layout(self) -> "N.mk_session_layout":
+        """What a block of this set's session records looks like (mk_session_layout_get)."""
+        lay = N.mk_session_layout()
+        N.check(N.lib().mk_session_layout_get(self._h, C.byref(lay)), "mk_session_layout_get")
+        return lay
+
+    def snapshot(self, index=None) -> "SessionSnapshot":
+        """The whole state of every instance, or of the listed ones (column t
+        is instance ``index[t]``): registers, ports, stacks, inChan / outChan,
+        the open call and the tier that holds it.  Reads the set, changes nothing."""
+        sel = self._index(index) if index is not None else None
+        m = self.n if sel is None else sel.size
+        lay = self.layout()
+        rec = np.zeros((lay.rows, m), np.uint32)
+        N.check(N.lib().mk_session_snapshot(self._h, sel.ctypes.data_as(C.c_void_p) if sel is not None else None, m,
+                                            rec.ctypes.data_as(C.c_void_p)), "mk_session_snapshot")
+        return SessionSnapshot(lay, rec)
+
+    def _layout_fits(self, lay):
+        own = self.layout()
+        for f in ("magic", "version", "net_hash", "nprog", "nstack", "stack_cap"):
+            if getattr(lay, f) != getattr(own, f):
+                raise ValueError(f"snapshot layout mismatch in {f}: the snapshot's {getattr(lay, f)}, "
+                                 f"this set's {getattr(own, f)}")
+        if lay.rows != own.rows - own.native_rows + lay.native_rows:
+            raise ValueError(f"snapshot layout mismatch in rows: {lay.rows} is not what its sections add up to")
+
+    def restore(self, snap: "SessionSnapshot", index=None, take=None):
+        """Overwrite every instance, or the listed ones, with records of
+        ``snap``: instance ``index[t]`` takes column ``take[t]`` (column t
+        without ``take``).  The snapshot may come from another set, GPU or
+        tier of the same network and stack_cap; a record goes back to the
+        native tier only in a set running the same native module, otherwise
+        the interpreter holds that instance from then on.  ValueError, with
+        nothing changed, for a layout of another network or a record out of
+        range."""
+        sel = self._index(index) if index is not None else None
+        m = self.n if sel is None else sel.size
+        self._layout_fits(snap.layout)
+        rec = np.ascontiguousarray(snap.rec, dtype=np.uint32)
+        if rec.ndim != 2 or rec.shape[0] != snap.layout.rows:
+            raise ValueError(f"snapshot block has shape {rec.shape}, its layout {snap.layout.rows} rows")
+        mcols = rec.shape[1]
+        col = None
+        if take is not None:
+            a = np.asarray(take)
+            if a.size and a.dtype.kind not in "iu":
+                raise ValueError(f"take must hold integers, got dtype {a.dtype}")
+            a = a.reshape(-1).astype(np.int64) if a.size else np.zeros(0, np.int64)
+            if a.size != m:
+                raise ValueError(f"take names {a.size} columns for {m} instances")
+            bad = (a < 0) | (a >= mcols)
+            if bad.any():
+                t = int(np.argmax(bad))
+                raise ValueError(f"take position {t}: {a[t]} is not a column of the snapshot's {mcols}")
+            col = np.ascontiguousarray(a.astype(np.uint32))
+        elif m > mcols:
+            raise ValueError(f"take position {mcols}: the snapshot has {mcols} columns for {m} instances")
+        rc = N.lib().mk_session_restore(self._h, sel.ctypes.data_as(C.c_void_p) if sel is not None else None, m,
+                                        C.byref(snap.layout), rec.ctypes.data_as(C.c_void_p), mcols,
+                                        col.ctypes.data_as(C.c_void_p) if col is not None else None)
+        if rc == N.MK_EINVAL:
+            raise ValueError("snapshot record out of range (held, an ip, a stack depth or the native superblock): "
+                             "nothing restored")
+        N.check(rc, "mk_session_restore")
+
+    def fork(self, src: int, index):
+        """Copy instance ``src`` into the listed instances: they continue
+        from its state, each on its own."""
+        if not 0 <= int(src) < self.n:
+            raise ValueError(f"fork source {src} is not an instance (n = {self.n})")
+        sel = self._index(index)
+        self.restore(self.snapshot(index=[int(src)]), index=sel, take=np.zeros(sel.size, np.int64))
+
+    def snapshot_device(self, rec_ptr, *, stream=None, index_ptr=None, m=None):
+        """:meth:`snapshot` into a device uint32 block [rows][m] (``rows``
+        from :meth:`layout`), asynchronous on ``stream``; ``index_ptr`` and
+        ``m`` as in :meth:`compute_device`."""
+        if (index_ptr is None) != (m is None):
+            raise ValueError("index_ptr and m go together")
+        N.check(N.lib().mk_session_snapshot_device(self._h, index_ptr, self.n if m is None else m, rec_ptr, stream),
+                "mk_session_snapshot_device")
+
+    def restore_device(self, layout, rec_ptr, mcols, *, stream=None, index_ptr=None, m=None, take_ptr=None):
+        """:meth:`restore` from a device block of ``mcols`` columns described
+        by ``layout``, asynchronous on ``stream``.  The block, ``index_ptr``
+        and ``take_ptr`` (device uint32 arrays of ``m`` entries) are taken on
+        trust; an entry out of range restores nothing."""
+        if (index_ptr is None) != (m is None):
+            raise ValueError("index_ptr and m go together")
+        self._layout_fits(layout)
+        N.check(N.lib().mk_session_restore_device(self._h, index_ptr, self.n if m is None else m, C.byref(layout),
+                                                  rec_ptr, mcols, take_ptr, stream), "mk_session_restore_device")
+
     def close(self):
         if getattr(self, "_h", None):
             N.lib().mk_session_free(self._h)
@@ -497,6 +592,64 @@ class SessionSet:
             self.close()
         except Exception:
             pass
+
+
+class SessionSnapshot:
+    """Session records out of a :class:`SessionSet` (include/mk.h, snapshots):
+    ``layout`` describes the block, ``rec`` is uint32[rows, m], column t one
+    instance's whole state."""
+
+    _HEAD = np.dtype("<u8")
+
+    def __init__(self, layout, rec):
+        self.layout, self.rec = layout, rec
+
+    @property
+    def m(self) -> int:
+        return self.rec.shape[1]
+
+    @property
+    def held(self) -> np.ndarray:
+        """Per record: the native tier held the instance (the interpreter: False)."""
+        return self.rec[0] == 1
+
+    def canonical(self, t: int) -> dict:
+        """Record t's canonical part, in the bytecode interpreter's terms."""
+        lay, r = self.layout, self.rec[:, t]
+
+        def i32(a):
+            return np.asarray(a, np.uint32).view(np.int32)
+
+        def i64(lo, hi):
+            return (np.asarray(lo, np.uint64) | (np.asarray(hi, np.uint64) << np.uint64(32))).view(np.int64)
+
+        node = r[9:9 + 10 * lay.nprog].reshape(lay.nprog, 10)
+        stacks = r[9 + 10 * lay.nprog:9 + 10 * lay.nprog + lay.nstack * (1 + lay.stack_cap)]
+        stacks = stacks.reshape(lay.nstack, 1 + lay.stack_cap)
+        io = int(r[1])
+        return dict(
+            held=int(r[0]), io=io, in_full=io & 1, out_full=(io >> 1) & 1, undeposited=(io >> 2) & 1,
+            call_open=(io >> 3) & 1, dead=(io >> 4) & 15, csteps=int(r[2]), pin=int(i32(r[3:4])[0]),
+            in_val=int(i32(r[4:5])[0]), out_val=int(i32(r[5:6])[0]), pend=int(r[6]) & 0xFFFF, hung=int(r[6]) >> 16,
+            pfull=int(r[7]) | int(r[8]) << 32, acc=i64(node[:, 0], node[:, 1]), bak=i64(node[:, 2], node[:, 3]),
+            ip=i32(node[:, 4]).copy(), pendv=i32(node[:, 5]).copy(), port=i32(node[:, 6:10]).copy(),
+            depth=stacks[:, 0].copy(), entries=i32(stacks[:, 1:]).copy())
+
+    def tobytes(self) -> bytes:
+        """The snapshot as bytes (layout, column count, block), for :meth:`frombytes`."""
+        return bytes(self.layout) + np.array([self.m], self._HEAD).tobytes() + \
+            np.ascontiguousarray(self.rec, dtype="<u4").tobytes()
+
+    @classmethod
+    def frombytes(cls, b: bytes) -> "SessionSnapshot":
+        k = C.sizeof(N.mk_session_layout)
+        if len(b) < k + 8:
+            raise ValueError("not a session snapshot: too short")
+        lay = N.mk_session_layout.from_buffer_copy(b[:k])
+        m = int(np.frombuffer(b[k:k + 8], cls._HEAD)[0])
+        if lay.magic != 0x52534B4D or len(b) != k + 8 + 4 * lay.rows * m:
+            raise ValueError("not a session snapshot: bad magic or size")
+        return cls(lay, np.frombuffer(b[k + 8:], "<u4").reshape(lay.rows, m).astype(np.uint32))
 
 
 def generate_inputs_device(n, out_ptr, *, seed, gen_kind=N.MK_GEN_FULL, gen_mask=0, offset=0, device=0, stream=None):
