@@ -329,6 +329,35 @@ int mk_session_reset_indexed(mk_session *s, const uint32_t *sel, size_t m);
  * session.  Synchronous. */
 int mk_session_call_open(mk_session *s, const uint32_t *sel, size_t m, uint8_t *open);
 
+/* ---- ragged bursts: each listed session its own number of calls -------------
+ * sel[0..m) as in the indexed forms; sel NULL with m == n: every session.
+ * off[0..m] (uint32_t) gives each entry's place in the I/O arrays: off[0] == 0,
+ * non-decreasing, off[m] == total < 2^32.  Entry t makes cnt = off[t+1] - off[t]
+ * sequential /compute calls on session sel[t], exactly as that many
+ * mk_session_compute_indexed calls on {sel[t]} would: call c of entry t takes
+ * in[off[t] + c] and reports out/status/steps[off[t] + c] -- the arrays are
+ * entry-major and compact, of length total (with every cnt 1, the indexed
+ * layout).  An entry with cnt 0 is not touched, like a session outside the
+ * list.  Within an entry the rules of a uniform burst hold: after a call that
+ * stays open (MK_ST_BUDGET) the later ones report MK_ST_CALL_OPEN and their
+ * inputs are not taken; after a stack overflow they report
+ * MK_ST_STACK_OVERFLOW with out 0.  m == 0 or total == 0 is MK_OK and
+ * launches nothing.  Resumes stay with mk_session_step_indexed.
+ *
+ * The host form checks the list and the offsets and returns MK_EINVAL for bad
+ * ones before anything is queued; it returns MK_EBUSY when a listed session
+ * with cnt >= 1 reported MK_ST_CALL_OPEN on its first call. */
+int mk_session_compute_ragged(mk_session *s, const uint32_t *sel, size_t m, const uint32_t *off, const int64_t *in,
+                              int32_t *out, uint8_t *status, uint32_t *steps);
+/* Device form, asynchronous on `stream`: d_sel and d_off (m + 1 words) are
+ * taken ON TRUST under the contract of mk_session_compute_indexed_device, and
+ * the arrays hold `total` words.  The only net below that contract: entry t
+ * is served only if d_sel[t] < n and d_off[t] <= d_off[t+1] <= total; one that
+ * is not loads nothing, stores nothing and writes no I/O word. */
+int mk_session_compute_ragged_device(mk_session *s, const uint32_t *d_sel, size_t m, const uint32_t *d_off,
+                                     size_t total, const int64_t *d_in, int32_t *d_out, uint8_t *d_status,
+                                     uint32_t *d_steps, void *stream);
+
 /* ---- snapshots: a session's state out of the set and back -------------------
  * A session record is one session's whole state -- registers, ports, pending
  * sends, stacks, inChan / outChan, its open call, the tier that holds it --

@@ -339,6 +339,48 @@ func (s *Sessions) StepIndexed(sel []uint32, in []int) (*Result, error) {
 	return r, nil
 }
 
+// ComputeRagged is a ragged burst in one launch: entry t makes len(in[t])
+// sequential /compute calls on instance sel[t] (sel nil: on instance t, with
+// one entry per instance), exactly as that many ComputeIndexed calls on it
+// alone would.  The result is flat and entry-major: call c of entry t is at
+// len(in[0]) + ... + len(in[t-1]) + c.  An entry without inputs is not
+// touched (mk_session_compute_ragged).
+func (s *Sessions) ComputeRagged(sel []uint32, in [][]int) (*Result, error) {
+	m := len(in)
+	if sel != nil && len(sel) != m {
+		return nil, fmt.Errorf("mk: %d entries for %d listed instances", m, len(sel))
+	}
+	if sel == nil && m != s.n {
+		return nil, fmt.Errorf("mk: %d entries for %d instances", m, s.n)
+	}
+	off := make([]uint32, m+1)
+	total := 0
+	for t, calls := range in {
+		total += len(calls)
+		if uint64(total) >= 1<<32 {
+			return nil, fmt.Errorf("mk: entry %d: 2^32 calls or more", t)
+		}
+		off[t+1] = uint32(total)
+	}
+	if total == 0 {
+		return &Result{}, nil
+	}
+	r := &Result{Out: make([]int32, total), Status: make([]uint8, total), Steps: make([]uint32, total)}
+	in64 := make([]int64, 0, total)
+	for _, calls := range in {
+		for _, v := range calls {
+			in64 = append(in64, int64(v))
+		}
+	}
+	rc := C.mk_session_compute_ragged(s.s, selPtr(sel), C.size_t(m), (*C.uint32_t)(unsafe.Pointer(&off[0])),
+		(*C.int64_t)(unsafe.Pointer(&in64[0])), (*C.int32_t)(unsafe.Pointer(&r.Out[0])),
+		(*C.uint8_t)(unsafe.Pointer(&r.Status[0])), (*C.uint32_t)(unsafe.Pointer(&r.Steps[0])))
+	if rc != C.MK_OK {
+		return nil, fmt.Errorf("mk_session_compute_ragged: %d", int(rc))
+	}
+	return r, nil
+}
+
 // ComputeIndexedDevice queues calls on device arrays ([call][m]; dSel a
 // device uint32 array taken on trust, unchanged until the launch completes),
 // asynchronous on `stream` (nil: the set's own) --

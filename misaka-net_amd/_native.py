@@ -140,6 +140,11 @@ SIGNATURES = {
     "mk_session_cancel_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mk_session_reset_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mk_session_call_open": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mk_session_compute_ragged": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_compute_ragged_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p]),
     "mk_session_layout_get": (C.c_int, [C.c_void_p, C.POINTER(mk_session_layout)]),
     "mk_session_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mk_session_snapshot_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),

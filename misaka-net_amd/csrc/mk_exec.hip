@@ -1001,8 +1001,13 @@ struct SessParams {
     // selected launches (mk_session_*_indexed, tis_session<NMAX, true>):
     // thread t of m owns session sel[t] and the I/O arrays have m columns,
     // [ncalls][m]; the state arrays keep their stride n
-    const uint32_t *sel; // [m] strictly increasing, every entry < n
+    const uint32_t *sel; // [m] strictly increasing, every entry < n (null: t itself)
     uint64_t m;
+    // ragged selected launches (mk_session_compute_ragged): entry t makes
+    // off[t+1] - off[t] calls, call c at word off[t] + c of the compact I/O
+    // arrays of length total; null: ncalls calls each, [ncalls][m]
+    const uint32_t *off; // [m + 1]
+    uint32_t total;
 };
 
 struct SessImportOut {
@@ -1062,8 +1067,27 @@ __device__ __forceinline__ void tis_session_one(const Insn *__restrict__ code, c
     const int tid = threadIdx.x;
     const uint64_t n = p.n;
     const uint64_t m = SEL ? p.m : n;
-    const uint64_t gid = SEL ? (t < m ? (uint64_t)p.sel[t] : n) : t; // the state index
-    int32_t *const port = lds;                     // [nprog*4][B]
+    // the state index, and the calls this entry makes.  A ragged entry
+    // (p.off) is live only with sel[t] < n and off[t] <= off[t+1] <= total;
+    // one that is not, or that has no call to make, touches nothing.
+    uint64_t gid = t;
+    uint32_t cnt = p.ncalls, io0 = 0u;
+    if (SEL) {
+        gid = n;
+        cnt = 0u;
+        if (t < m) {
+            gid = p.sel ? (uint64_t)p.sel[t] : t;
+            cnt = p.ncalls;
+            if (p.off) {
+                const uint32_t o0 = p.off[t], o1 = p.off[t + 1];
+                const bool ok = gid < n && o0 < o1 && o1 <= p.total;
+                io0 = o0;
+                cnt = ok ? o1 - o0 : 0u;
+                if (!ok) gid = n;
+            }
+        }
+    }
+    int32_t *const port = lds;                    // [nprog*4][B]
     int32_t *const sdepth = lds + p.nprog * 4 * B; // [nstack][B]
     if (handed) sess_import_one(p.imp, p, gid);
     const bool live = gid < n && (!p.nsb || p.nsb[gid] == kSessT1);
@@ -1101,8 +1125,12 @@ __device__ __forceinline__ void tis_session_one(const Insn *__restrict__ code, c
     const uint32_t c0 = fresh ? p.hand_call[gid] : 0u;
     // ncalls sequential /compute calls, the state carried in registers/LDS
     // from one to the next (a burst of requests on one instance, one launch)
-    for (uint32_t call = 0; call < p.ncalls; ++call) {
-    const uint64_t ci = (uint64_t)call * m + t;
+    // A selected launch runs to the wave's largest count (the round loop
+    // below is wave-wide, so every lane takes the same trips); a lane past
+    // its own count (`due` false) sits the call out and writes no I/O.
+    for (uint32_t call = 0; SEL ? __ballot(call < cnt) != 0ull : call < p.ncalls; ++call) {
+    const bool due = !SEL || call < cnt;
+    const uint64_t ci = SEL && p.off ? (uint64_t)io0 + call : (uint64_t)call * m + t;
     // io bit 3: a call is open (it parked on peers or ran out of its slice's
     // budget); bit 2: its input is not deposited yet (held in pin).  A resume
     // continues it with its input and step count; a new call while one is
@@ -1112,8 +1140,8 @@ __device__ __forceinline__ void tis_session_one(const Insn *__restrict__ code, c
     // of the burst were answered by the native kernel)
     const bool handed = fresh && call == c0, skip = fresh && call < c0;
     const bool resumed = (p.resume || handed) && open;
-    const bool ran = live && !skip && dead == 0 && (p.resume || handed ? resumed : !open);
-    const int32_t x = !live ? 0 : resumed ? p.pin[gid] : (int32_t)p.in[ci]; // int32(v) at GetInput (master.go:237)
+    const bool ran = live && due && !skip && dead == 0 && (p.resume || handed ? resumed : !open);
+    const int32_t x = !live || !due ? 0 : resumed ? p.pin[gid] : (int32_t)p.in[ci]; // int32(v) at GetInput (master.go:237)
     bool active = ran, got = false;
     bool deposited = resumed && !((io >> 2) & 1u);
     int32_t result = 0;
@@ -1311,7 +1339,7 @@ __device__ __forceinline__ void tis_session_one(const Insn *__restrict__ code, c
             }
         }
     }
-    if (live && !skip) {
+    if (live && due && !skip) {
         p.out[ci] = got ? result : 0;
         p.status[ci] = (uint8_t)(got ? MK_ST_HAS_OUTPUT : ran ? reason : dead ? dead : open && !p.resume ? MK_ST_CALL_OPEN : 0u);
         if (p.steps) p.steps[ci] = ran ? steps : 0u;
@@ -1330,7 +1358,7 @@ __device__ __forceinline__ void tis_session_one(const Insn *__restrict__ code, c
         p.out[ci] = 0;
         p.status[ci] = p.nsb[gid] == kSessDead ? (uint8_t)MK_ST_STACK_OVERFLOW : (uint8_t)0;
         if (p.steps) p.steps[ci] = 0u;
-    } else if (SEL && t < m && gid >= n) { // a listed entry that names no session
+    } else if (SEL && due && gid >= n) { // a listed entry that names no session
         p.out[ci] = 0;
         p.status[ci] = (uint8_t)0;
         if (p.steps) p.steps[ci] = 0u;
@@ -3706,6 +3734,8 @@ struct SessKSel {
     SessK k;
     const uint32_t *sel;
     uint64_t m;
+    const uint32_t *off;
+    uint32_t total;
 };
 
 // *queued (when given) is set once a kernel has been queued on `stream`, so
@@ -3716,15 +3746,22 @@ struct SessKSel {
 // ~3 us of stream time per call (round 6, profiles/r08_sessions_ab.txt).
 // With d_sel the launch is a selected one: m threads, thread t on session
 // d_sel[t], the I/O arrays [ncalls][m]; the grids cover m, not n.
+// With d_off the launch is selected and ragged (mk_session_compute_ragged):
+// entry t makes d_off[t+1] - d_off[t] calls, the I/O arrays are compact, of
+// length total, ncalls is not used, and a null d_sel lists every session.
 int session_launch(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *d_status, uint32_t *d_steps,
                    hipStream_t stream, uint32_t ncalls = 1, bool resume = false, bool *queued = nullptr,
-                   hipEvent_t done = nullptr, const uint32_t *d_sel = nullptr, uint64_t m = 0)
+                   hipEvent_t done = nullptr, const uint32_t *d_sel = nullptr, uint64_t m = 0,
+                   const uint32_t *d_off = nullptr, uint32_t total = 0)
 {
     if (s->broken) return MK_EDEVICE;
-    if (s->n == 0 || ncalls == 0 || (d_sel && m == 0)) return MK_OK;
+    const bool sel = d_sel || d_off;
+    if (s->n == 0 || ncalls == 0 || (sel && m == 0) || (d_off && total == 0)) return MK_OK;
     SessParams p = s->p;
     p.sel = d_sel;
     p.m = m;
+    p.off = d_off;
+    p.total = total;
     p.ncalls = ncalls;
     p.resume = resume ? 1u : 0u;
     p.in = d_in;
@@ -3733,22 +3770,22 @@ int session_launch(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *
     p.steps = d_steps;
     const Insn *code = s->h->dev[s->device].d_code;
     const size_t lds = (size_t)(s->nprog * 4 + s->nstack) * kBlock * 4;
-    const uint64_t blocks = ((d_sel ? m : (uint64_t)s->n) + kBlock - 1) / kBlock;
+    const uint64_t blocks = ((sel ? m : (uint64_t)s->n) + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffull) return MK_ELIMIT;
     // hipExtModuleLaunchKernel takes the grid in threads, 32 bits
-    if (d_sel && blocks * kBlock > 0xffffffffull) return MK_ELIMIT;
+    if (sel && blocks * kBlock > 0xffffffffull) return MK_ELIMIT;
     const uint64_t iblocks = blocks < kSessGridCap ? blocks : kSessGridCap; // the interpreter's grid-stride grid
     if (s->native && !resume) {
         if (++s->epoch == 0) s->epoch = 1; // sflags[0] starts at 0: "no hand-off yet"
         // 1. the native kernel: every session it holds, every call of the burst
         SessK k{s->n, ncalls, p.budget, d_in, d_out, d_status, d_steps, s->nsb, s->regs, s->slots,
                 s->hand_sb, s->hand_steps, s->hand_call, s->sflags, s->epoch};
-        SessKSel ks{k, d_sel, m};
-        void *kargs[] = {d_sel ? (void *)&ks : (void *)&k};
+        SessKSel ks{k, d_sel, m, d_off, total};
+        void *kargs[] = {sel ? (void *)&ks : (void *)&k};
         // the native kernel is the launch's last when the interpreter pass is
         // skipped (below: no call can reach the budget)
         const bool last = s->call_steps < (uint64_t)p.budget && !s->interp_may_hold;
-        if (hipExtModuleLaunchKernel(d_sel ? s->fn_sel : s->fn, (uint32_t)(blocks * kBlock), 1, 1, kBlock, 1, 1, 0,
+        if (hipExtModuleLaunchKernel(sel ? s->fn_sel : s->fn, (uint32_t)(blocks * kBlock), 1, 1, kBlock, 1, 1, 0,
                                      stream, kargs, nullptr, nullptr, last ? done : nullptr, 0) != hipSuccess)
             return MK_EDEVICE;
         if (queued) *queued = true;
@@ -3763,7 +3800,7 @@ int session_launch(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *
     }
     // 3. the interpreter: its sessions (all of them without the native tier)
     void *args[] = {(void *)&code, (void *)&p};
-    if (hipExtLaunchKernel(pick_session_kernel(s->nprog, d_sel != nullptr), dim3((unsigned)iblocks), dim3(kBlock), args,
+    if (hipExtLaunchKernel(pick_session_kernel(s->nprog, sel), dim3((unsigned)iblocks), dim3(kBlock), args,
                            lds, stream, nullptr, done, 0) != hipSuccess) {
         if (s->native && !resume) s->broken = true;
         return MK_EDEVICE;
@@ -4582,6 +4619,97 @@ int mk_session_compute_indexed_device(mk_session *s, const uint32_t *d_sel, size
     if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
     int rc = mk::session_launch(s, d_in, d_out, d_status, d_steps, st, (uint32_t)ncalls, false, &queued, s->order,
                                 d_sel, m);
+    if (rc) {
+        if (queued) (void)mk::session_mark(s, st);
+        return rc;
+    }
+    s->last = st;
+    return MK_OK;
+}
+
+// ---- ragged bursts: each listed session its own number of calls -------------
+extern "C++" {
+namespace mk {
+namespace {
+// session_host_calls_sel for a ragged burst: the staging holds in, out,
+// steps, status (off[m] words each), then off and, when given, sel.
+int session_host_calls_ragged(mk_session *s, const uint32_t *sel, size_t m, const uint32_t *off, const int64_t *in,
+                              int32_t *out, uint8_t *status, uint32_t *steps)
+{
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (sel ? !sel_valid(s, sel, m) : m != s->n) return MK_EINVAL; // a null list: every session, m == n
+    if (m == 0) return MK_OK;
+    if (off[0] != 0u) return MK_EINVAL;
+    for (size_t t = 0; t < m; t++)
+        if (off[t + 1] < off[t]) return MK_EINVAL;
+    const size_t c = off[m];
+    if (c == 0) return MK_OK;
+    if (!in || !out || !status) return MK_EINVAL;
+    mk::DeviceGuard g(s->device);
+    if (int rc = session_wait_last(s, s->stream)) return rc;
+    const size_t a8 = al256(c * 8), a4 = al256(c * 4), a1 = al256(c), o_off = a8 + a4 + a4 + a1;
+    const size_t o_sel = o_off + al256((m + 1) * 4);
+    if (int rc = session_stage(s, o_sel + (sel ? al256(m * 4) : 0))) return rc;
+    char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
+    int64_t *din = (int64_t *)b;
+    int32_t *dout = (int32_t *)(b + a8);
+    uint32_t *dsteps = (uint32_t *)(b + a8 + a4);
+    uint8_t *dst = (uint8_t *)(b + a8 + a4 + a4);
+    uint32_t *doff = (uint32_t *)(b + o_off);
+    uint32_t *dsel = sel ? (uint32_t *)(b + o_sel) : nullptr;
+    memcpy(hb, in, c * 8);
+    memcpy(hb + o_off, off, (m + 1) * 4);
+    if (sel) memcpy(hb + o_sel, sel, m * 4);
+    if (hipMemcpyAsync(din, hb, c * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipMemcpyAsync(doff, hb + o_off, (m + 1) * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        (sel && hipMemcpyAsync(dsel, hb + o_sel, m * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess))
+        return MK_EDEVICE;
+    int rc = session_launch(s, din, dout, dst, steps ? dsteps : nullptr, s->stream, 1, false, nullptr, nullptr, dsel, m,
+                            doff, (uint32_t)c);
+    if (rc) return rc;
+    if (hipMemcpyAsync(hb + a8, dout, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipMemcpyAsync(hb + a8 + a4 + a4, dst, c, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    if (steps && hipMemcpyAsync(hb + a8 + a4, dsteps, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
+    memcpy(out, hb + a8, c * 4);
+    memcpy(status, hb + a8 + a4 + a4, c);
+    if (steps) memcpy(steps, hb + a8 + a4, c * 4);
+    // a listed session with a call to make that had one open when this launch
+    // began did nothing: its first call says so
+    for (size_t t = 0; t < m; t++)
+        if (off[t + 1] > off[t] && status[off[t]] == MK_ST_CALL_OPEN) return MK_EBUSY;
+    return MK_OK;
+}
+} // namespace
+} // namespace mk
+}
+
+int mk_session_compute_ragged(mk_session *s, const uint32_t *sel, size_t m, const uint32_t *off, const int64_t *in,
+                              int32_t *out, uint8_t *status, uint32_t *steps)
+{
+    if (!s || (m && !off)) return MK_EINVAL;
+    return mk::session_host_calls_ragged(s, sel, m, off, in, out, status, steps);
+}
+
+int mk_session_compute_ragged_device(mk_session *s, const uint32_t *d_sel, size_t m, const uint32_t *d_off,
+                                     size_t total, const int64_t *d_in, int32_t *d_out, uint8_t *d_status,
+                                     uint32_t *d_steps, void *stream)
+{
+    if (!s || (m && total && (!d_off || !d_in || !d_out || !d_status))) return MK_EINVAL;
+    if (total > 0xffffffffull || m > s->n || (!d_sel && m && m != s->n)) return MK_EINVAL;
+    if (m == 0 || total == 0) return MK_OK;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::DeviceGuard g(s->device);
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    // ordered against every other launch of the set, whatever it selected
+    // (mk_session_compute_seq_device)
+    if (int rc = mk::session_wait_last(s, st)) return rc;
+    bool queued = false;
+    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
+    int rc = mk::session_launch(s, d_in, d_out, d_status, d_steps, st, 1, false, &queued, s->order, d_sel, m, d_off,
+                                (uint32_t)total);
     if (rc) {
         if (queued) (void)mk::session_mark(s, st);
         return rc;

@@ -2957,12 +2957,18 @@ struct SessK {
     uint32_t *sflags;    // [0]: this launch's epoch once a lane handed off (mk_exec.hip SessParams)
     uint32_t epoch;
 };
-// The selected launch (mk_session_*_indexed): m threads, thread t on session
-// sel[t] (strictly increasing, so no two threads share a session).
+// The selected launch (mk_session_*_indexed, mk_session_compute_ragged):
+// m threads, thread t on session sel[t] (strictly increasing, so no two
+// threads share a session; null: t itself).  With off the launch is ragged:
+// entry t makes off[t+1] - off[t] calls, its I/O words at off[t] + call of
+// the compact arrays of length total; without, k.ncalls calls each, the
+// arrays [ncalls][m].
 struct SessKSel {
     SessK k;
-    const uint32_t *sel; // [m]
+    const uint32_t *sel; // [m] or null
     uint64_t m;
+    const uint32_t *off; // [m + 1] or null
+    uint32_t total;
 };
 )";
 
@@ -2970,8 +2976,9 @@ struct SessKSel {
 // $ places): thread t of a launch answers I/O column t of the launch's
 // columns and owns session gid -- t itself of n columns in the plain entry,
 // sel[t] of m in the selected one.  State is indexed by gid (stride n), I/O
-// by call * columns + t.  The plain entry's text is what it was before the
-// selected one existed, so that its code is too.
+// by call * columns + t (a ragged selected launch: off[t] + call).  The plain
+// entry's text is what it was before the selected one existed, so that its
+// code is too.
 const char *const kSessionKernel = R"(
 extern "C" __global__ void __launch_bounds__(256) $ENTRY
 {
@@ -2982,9 +2989,9 @@ $INDEX
     MkLane L;
     mk_sess_load(L, p.regs, gid, p.n, native);
     int32_t *slots = p.slots ? p.slots + gid : (int32_t *)0;
-    for (uint32_t call = 0; call < p.ncalls; ++call) {
-        const uint64_t ci = (uint64_t)call * $COLS + $COL;
-        const bool run = sbv < MK_SS_DEAD;
+    for (uint32_t call = 0; call < $NCALLS; ++call) {
+        const uint64_t ci = $CI;
+        const bool run = $RUN;
         L.sb = run ? sbv : MK_SB_IDLE;
         L.steps = 0u;
         L.st = 0u;
@@ -3041,16 +3048,34 @@ $NOSESSION
 std::string session_kernel(bool sel)
 {
     // an entry of the list that is >= n names no session: not live, it loads
-    // and stores no state and reports out 0 / status 0
+    // and stores no state and reports out 0 / status 0.  A ragged entry
+    // (q.off) is live only with sel[t] < n and off[t] <= off[t+1] <= total;
+    // one that is not, or that has no call to make, loads nothing, stores
+    // nothing and writes no I/O word (cnt 0).  The call loop of a ragged
+    // launch runs to the wave's largest count -- its sweep and rounds are
+    // wave-wide -- and a lane past its own count sits the call out: no input,
+    // no I/O, sbv as it is.  A uniform launch keeps ncalls as its bound and
+    // pays no reduction.
     const std::pair<const char *, const char *> fill[] = {
         {"$ENTRY", sel ? "mk_sess_exec_sel(SessKSel q)" : "mk_sess_exec(SessK p)"},
         {"$INDEX", sel ? "    const SessK &p = q.k;\n"
                          "    const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;\n"
-                         "    const uint64_t gid = t < q.m ? (uint64_t)q.sel[t] : p.n;"
+                         "    uint64_t gid = t < q.m ? (q.sel ? (uint64_t)q.sel[t] : t) : p.n;\n"
+                         "    uint32_t cnt = t < q.m ? p.ncalls : 0u, io0 = 0u, wcalls = p.ncalls;\n"
+                         "    if (q.off) { // the same for the whole launch\n"
+                         "        const uint32_t o0 = t < q.m ? q.off[t] : 0u, o1 = t < q.m ? q.off[t + 1] : 0u;\n"
+                         "        const bool ok = gid < p.n && o0 < o1 && o1 <= q.total;\n"
+                         "        io0 = o0;\n"
+                         "        cnt = ok ? o1 - o0 : 0u;\n"
+                         "        if (!ok) gid = p.n;\n"
+                         "        wcalls = MK_WAVE_MAX(cnt);\n"
+                         "    }"
                        : "    const uint64_t gid = (uint64_t)blockIdx.x * 256u + threadIdx.x;"},
-        {"$COLS", sel ? "q.m" : "p.n"}, // before $COL, its prefix
-        {"$COL", sel ? "t" : "gid"},
-        {"$NOSESSION", sel ? "        if (t < q.m && !live) {\n"
+        {"$NCALLS", sel ? "wcalls" : "p.ncalls"},
+        {"$CI", sel ? "q.off ? (uint64_t)io0 + call : (uint64_t)call * q.m + t" : "(uint64_t)call * p.n + gid"},
+        {"$RUN", sel ? "sbv < MK_SS_DEAD && call < cnt" : "sbv < MK_SS_DEAD"},
+        {"$NOSESSION", sel ? "        if (call >= cnt) continue;\n"
+                             "        if (!live) {\n"
                              "            p.out[ci] = 0;\n"
                              "            p.status[ci] = (uint8_t)0;\n"
                              "            if (p.steps) p.steps[ci] = 0u;\n"

@@ -477,6 +477,88 @@ class SessionSet:
         N.check(N.lib().mk_session_compute_seq_device(self._h, in_ptr, ncalls, out_ptr, status_ptr, steps_ptr, stream),
                 "mk_session_compute_seq_device")
 
+    @staticmethod
+    def _ragged(values, counts):
+        """A ragged burst's flat inputs and offsets (uint32, ``m + 1`` of
+        them) from ``values`` and ``counts``; ValueError names the first
+        offending position."""
+        if counts is None:
+            rows = [np.asarray(r, dtype=np.int64).reshape(-1) for r in values]
+            cnt = np.array([r.size for r in rows], np.int64)
+            v = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+        else:
+            c = np.asarray(counts).reshape(-1)
+            if c.size and c.dtype.kind not in "iu":
+                each = list(counts) if not isinstance(counts, np.ndarray) else list(c)
+                t = next((i for i, x in enumerate(each) if not isinstance(x, (int, np.integer)) or
+                          isinstance(x, (bool, np.bool_))), 0)
+                raise ValueError(f"counts position {t}: {each[t]!r} is not an integer")
+            cnt = c.astype(np.int64) if c.size else np.zeros(0, np.int64)
+            if (cnt < 0).any():
+                t = int(np.argmax(cnt < 0))
+                raise ValueError(f"counts position {t}: {cnt[t]} is negative")
+            v = np.asarray(values, dtype=np.int64).reshape(-1)
+        off = np.zeros(cnt.size + 1, np.int64)
+        np.cumsum(cnt, out=off[1:])
+        if off[-1] >= 1 << 32:
+            t = int(np.argmax(off[1:] >= 1 << 32))
+            raise ValueError(f"counts position {t}: the calls up to here number {off[t + 1]}, 2^32 or more")
+        if v.size != off[-1]:
+            # the entry whose calls the values end in, or past the last entry
+            t = int(np.searchsorted(off[1:], v.size, side="right")) if v.size < off[-1] else cnt.size
+            raise ValueError(f"counts position {t}: {v.size} values for {int(off[-1])} calls "
+                             f"(len(values) != sum(counts))")
+        return np.ascontiguousarray(v), np.ascontiguousarray(off.astype(np.uint32))
+
+    def compute_ragged(self, values, counts=None, *, index=None, steps=True, busy_ok=False) -> BatchResult:
+        """A ragged burst in one launch: entry t makes ``counts[t]`` sequential
+        /compute calls on instance ``index[t]`` (t itself without ``index``),
+        exactly as that many :meth:`compute` calls on it alone would
+        (mk_session_compute_ragged).  With ``counts``, ``values`` is flat and
+        entry-major -- entry t's inputs at ``sum(counts[:t])`` onwards --
+        and without, a sequence of per-entry sequences.  The result holds flat
+        arrays in the same order.  An entry with count 0 is not touched.
+        MkError(MK_EBUSY) unless ``busy_ok`` when a listed instance with a
+        call to make had one open."""
+        v, off = self._ragged(values, counts)
+        sel = self._index(index) if index is not None else None
+        m = self.n if sel is None else sel.size
+        if off.size - 1 != m:
+            raise ValueError(f"expected {m} entries, got {off.size - 1}")
+        total = int(off[-1])
+        out = np.zeros(total, np.int32)
+        st = np.zeros(total, np.uint8)
+        sp = np.zeros(total, np.uint32) if steps else None
+        if total:
+            rc = N.lib().mk_session_compute_ragged(
+                self._h, sel.ctypes.data_as(C.c_void_p) if sel is not None else None, m,
+                off.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                st.ctypes.data_as(C.c_void_p), sp.ctypes.data_as(C.c_void_p) if sp is not None else None)
+            if not (busy_ok and rc == N.MK_EBUSY):
+                N.check(rc, "mk_session_compute_ragged")
+        return BatchResult(out, st, sp)
+
+    def compute_ragged_device(self, in_ptr, off_ptr, total, out_ptr, status_ptr, steps_ptr=None, *, stream=None,
+                              index_ptr=None, m=None):
+        """A ragged burst on device arrays, asynchronous on ``stream``
+        (mk_session_compute_ragged_device): ``off_ptr`` is a device uint32
+        array of ``m + 1`` offsets (0 first, non-decreasing, ``total`` last),
+        the I/O arrays hold ``total`` words, entry-major.  ``index_ptr`` and
+        ``m`` as in :meth:`compute_device`; without them every instance is
+        listed.  Offsets and list are taken on trust and kept unchanged until
+        the launch completes."""
+        if (index_ptr is None) != (m is None):
+            raise ValueError("index_ptr and m go together")
+        if m is None:
+            m = self.n
+        if not 0 <= m <= self.n:
+            raise ValueError(f"m = {m} outside [0, {self.n}]")
+        if not 0 <= total < 1 << 32:
+            raise ValueError(f"total = {total} outside [0, 2^32)")
+        N.check(N.lib().mk_session_compute_ragged_device(self._h, index_ptr, m, off_ptr, total, in_ptr, out_ptr,
+                                                         status_ptr, steps_ptr, stream),
+                "mk_session_compute_ragged_device")
+
     def reset(self, *, index=None):
         """/reset (master.go:126-143): every instance back to its initial
         state; with ``index``, the listed instances only."""
