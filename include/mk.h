@@ -358,6 +358,52 @@ int mk_session_compute_ragged_device(mk_session *s, const uint32_t *d_sel, size_
                                      size_t total, const int64_t *d_in, int32_t *d_out, uint8_t *d_status,
                                      uint32_t *d_steps, void *stream);
 
+/* ---- request queues: arrival order in, grouped on the GPU --------------------
+ * A queue is `total` < 2^32 requests in arrival order: request j is for
+ * session ids[j] (any order, repeats allowed), carries in[j] and is answered
+ * at out[j], status[j], steps[j].  The launch behaves exactly as if the
+ * requests were served one at a time in arrival order, each as a one-entry
+ * mk_session_compute_indexed call on {ids[j]}: sessions are independent, the
+ * requests of one session run in arrival order, every answer returns to its
+ * own position.  Within one session the rules of a burst hold, as in a ragged
+ * entry (MK_ST_CALL_OPEN after a call that stays open, its input not taken;
+ * MK_ST_STACK_OVERFLOW with out 0 after an overflow).  A session with no
+ * request is not touched.  total == 0 is MK_OK and launches nothing.  The
+ * grouping -- a stable sort by session and a compaction -- runs on the GPU and
+ * feeds one ragged launch: whatever mk_session_compute_ragged accepts or
+ * refuses for a set the queue forms do likewise, and they order against every
+ * other launch of the set as the ragged forms do.
+ *
+ * The host form returns MK_EINVAL for any ids[j] >= n before anything is
+ * queued, and MK_EBUSY when a request that is the first of its session in
+ * this queue reported MK_ST_CALL_OPEN. */
+int mk_session_compute_queue(mk_session *s, const uint32_t *ids, const int64_t *in, size_t total, int32_t *out,
+                             uint8_t *status, uint32_t *steps /* nullable */);
+/* Device form, asynchronous on `stream`, no host synchronisation unless the
+ * set's queue scratch has to grow (it never shrinks; MK_ENOMEM leaves the set
+ * usable).  d_ids is taken ON TRUST; the net: a request with d_ids[j] >= n
+ * touches no session -- whatever its low bits -- and reports out 0, status 0,
+ * steps 0. */
+int mk_session_compute_queue_device(mk_session *s, const uint32_t *d_ids, const int64_t *d_in, size_t total,
+                                    int32_t *d_out, uint8_t *d_status, uint32_t *d_steps, void *stream);
+/* The grouping alone, for any n in [1, 2^32 - 1], on `device`, asynchronous on
+ * `stream`.  With key[j] = min(d_ids[j], n) and M = min(total, n):
+ *   d_perm[0..total)  the stable order of the keys: key[perm[k]] non-decreasing,
+ *                     ties in increasing j (numpy argsort, kind="stable")
+ *   *d_m              the number of distinct keys below n
+ *   d_sel[0..M)       those m keys, increasing, then 0xffffffff
+ *   d_off[0..M]       for t < m the first k with key[perm[k]] == sel[t]; for
+ *                     m <= t <= M the number of requests with an id below n
+ * so that (d_sel, M, d_off, total) is a ragged launch over the requests in
+ * perm order whose padded entries the ragged guard drops.  d_tmp: scratch of
+ * at least the bytes mk_requests_group_tmp_bytes reports, 4-byte aligned.
+ * MK_EINVAL for n == 0, total >= 2^32, a null pointer with total > 0 or a
+ * scratch too small; total == 0 writes *d_m = 0 and d_off[0] = 0. */
+int mk_requests_group_tmp_bytes(uint32_t n, size_t total, size_t *bytes);
+int mk_requests_group_device(int device, uint32_t n, const uint32_t *d_ids, size_t total, uint32_t *d_perm,
+                             uint32_t *d_sel, uint32_t *d_off, uint32_t *d_m, void *d_tmp, size_t tmp_bytes,
+                             void *stream);
+
 /* ---- snapshots: a session's state out of the set and back -------------------
  * A session record is one session's whole state -- registers, ports, pending
  * sends, stacks, inChan / outChan, its open call, the tier that holds it --

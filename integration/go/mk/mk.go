@@ -381,6 +381,32 @@ func (s *Sessions) ComputeRagged(sel []uint32, in [][]int) (*Result, error) {
 	return r, nil
 }
 
+// ComputeQueue serves a request queue in arrival order in one launch: request
+// j is one /compute call with in[j] on instance ids[j] -- any order, repeats
+// allowed -- exactly as if the requests were served one at a time, and
+// result j is request j's.  The grouping by instance runs on the GPU
+// (mk_session_compute_queue).
+func (s *Sessions) ComputeQueue(ids []uint32, in []int64) (*Result, error) {
+	total := len(ids)
+	if len(in) != total {
+		return nil, fmt.Errorf("mk: %d inputs for %d requests", len(in), total)
+	}
+	if total == 0 {
+		return &Result{}, nil
+	}
+	if uint64(total) >= 1<<32 {
+		return nil, fmt.Errorf("mk: 2^32 requests or more")
+	}
+	r := &Result{Out: make([]int32, total), Status: make([]uint8, total), Steps: make([]uint32, total)}
+	rc := C.mk_session_compute_queue(s.s, (*C.uint32_t)(unsafe.Pointer(&ids[0])), (*C.int64_t)(unsafe.Pointer(&in[0])),
+		C.size_t(total), (*C.int32_t)(unsafe.Pointer(&r.Out[0])), (*C.uint8_t)(unsafe.Pointer(&r.Status[0])),
+		(*C.uint32_t)(unsafe.Pointer(&r.Steps[0])))
+	if rc != C.MK_OK {
+		return nil, fmt.Errorf("mk_session_compute_queue: %d", int(rc))
+	}
+	return r, nil
+}
+
 // ComputeIndexedDevice queues calls on device arrays ([call][m]; dSel a
 // device uint32 array taken on trust, unchanged until the launch completes),
 // asynchronous on `stream` (nil: the set's own) --

@@ -14,6 +14,8 @@ from .network import (
     SessionSnapshot,
     TisParseError,
     generate_inputs_device,
+    group_requests_device,
+    group_requests_tmp_bytes,
     tokenize,
     valu_probe_device,
 )
@@ -27,6 +29,8 @@ __all__ = [
     "SessionSnapshot",
     "TisParseError",
     "generate_inputs_device",
+    "group_requests_device",
+    "group_requests_tmp_bytes",
     "tokenize",
     "valu_probe_device",
     "networks",

@@ -145,6 +145,14 @@ SIGNATURES = {
     "mk_session_compute_ragged_device": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                   C.c_void_p, C.c_void_p]),
+    "mk_session_compute_queue": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_compute_queue_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_requests_group_tmp_bytes": (C.c_int, [C.c_uint32, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "mk_requests_group_device": (
+        C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "mk_session_layout_get": (C.c_int, [C.c_void_p, C.POINTER(mk_session_layout)]),
     "mk_session_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mk_session_snapshot_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),

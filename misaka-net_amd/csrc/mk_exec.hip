@@ -69,6 +69,7 @@ extern char **environ;
 #define MK_HD __host__ __device__
 #include "sess_convert.h"
 #include "sess_record.h"
+#include "req_group.h"
 
 namespace mk {
 
@@ -3652,6 +3653,11 @@ struct mk_session {
     void *d_stage = nullptr; // host-API staging: in, out, status, steps
     void *h_stage = nullptr; // pinned host mirror of d_stage
     size_t stage_bytes = 0;
+    // request queues (mk_session_compute_queue, req_group.h): the grouping's
+    // scratch and outputs and the sorted I/O arrays, one allocation with room
+    // for queue_cap requests, grown on demand
+    void *d_queue = nullptr;
+    size_t queue_cap = 0;
     hipStream_t stream = nullptr;
     mk::SessParams p{};
     // native tier (tis_jit.h mk_sess_exec): the session schedule compiled to
@@ -3705,6 +3711,7 @@ struct mk_session {
         (void)hipFree(d_native);
         (void)hipFree(d_stage);
         (void)hipHostFree(h_stage);
+        (void)hipFree(d_queue);
         mk::release_module(mod, rtc_from);
         if (order) (void)hipEventDestroy(order);
         if (stream) (void)hipStreamDestroy(stream);
@@ -4716,6 +4723,203 @@ int mk_session_compute_ragged_device(mk_session *s, const uint32_t *d_sel, size_
     }
     s->last = st;
     return MK_OK;
+}
+
+// ---- request queues: arrival order in, grouped on the GPU (req_group.h) -------
+int mk_requests_group_tmp_bytes(uint32_t n, size_t total, size_t *bytes)
+{
+    if (!bytes || n == 0 || total > 0xffffffffull) return MK_EINVAL;
+    *bytes = mk::rg::rg_tmp_layout(total).bytes;
+    return MK_OK;
+}
+
+int mk_requests_group_device(int device, uint32_t n, const uint32_t *d_ids, size_t total, uint32_t *d_perm,
+                             uint32_t *d_sel, uint32_t *d_off, uint32_t *d_m, void *d_tmp, size_t tmp_bytes,
+                             void *stream)
+{
+    if (n == 0 || total > 0xffffffffull || !d_off || !d_m) return MK_EINVAL;
+    if (total && (!d_ids || !d_perm || !d_sel || !d_tmp)) return MK_EINVAL;
+    if (total && tmp_bytes < mk::rg::rg_tmp_layout(total).bytes) return MK_EINVAL;
+    const int ndev = mk::device_count();
+    if (ndev <= 0) return MK_EDEVICE;
+    if (device < 0 || device >= ndev) return MK_EINVAL;
+    mk::DeviceGuard g(device);
+    hipStream_t st = (hipStream_t)stream;
+    if (total == 0) {
+        if (hipMemsetAsync(d_m, 0, 4, st) != hipSuccess || hipMemsetAsync(d_off, 0, 4, st) != hipSuccess)
+            return MK_EDEVICE;
+        return MK_OK;
+    }
+    return mk::rg::rg_group(n, d_ids, (uint32_t)total, d_perm, d_sel, d_off, d_m, d_tmp, st);
+}
+
+extern "C++" {
+namespace mk {
+namespace {
+// The queue scratch of a set, for `total` requests.
+struct QueueBufs {
+    void *tmp;
+    uint32_t *perm, *sel, *off, *m;
+    int64_t *in;
+    int32_t *out;
+    uint32_t *steps;
+    uint8_t *status;
+    size_t bytes;
+};
+
+QueueBufs queue_layout(size_t n, size_t total, void *base)
+{
+    const size_t M = total < n ? total : n;
+    size_t at = 0;
+    auto take = [&](size_t b) {
+        const size_t o = at;
+        at += al256(b ? b : 1);
+        return (char *)base + o;
+    };
+    QueueBufs q{};
+    q.tmp = take(rg::rg_tmp_layout(total).bytes);
+    q.perm = (uint32_t *)take(total * 4);
+    q.sel = (uint32_t *)take(M * 4);
+    q.off = (uint32_t *)take((M + 1) * 4);
+    q.m = (uint32_t *)take(4);
+    q.in = (int64_t *)take(total * 8);
+    q.out = (int32_t *)take(total * 4);
+    q.steps = (uint32_t *)take(total * 4);
+    q.status = (uint8_t *)take(total);
+    q.bytes = at;
+    return q;
+}
+
+// Room for `total` requests.  Growing waits for the set's last launch -- it
+// may be reading the old scratch -- then frees and reallocates; a failed
+// allocation leaves the set without a scratch and usable.  Caller holds s->mu.
+int queue_reserve(mk_session *s, size_t total)
+{
+    if (total <= s->queue_cap) return MK_OK;
+    if (s->last && s->order && hipEventSynchronize(s->order) != hipSuccess) return MK_EDEVICE;
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
+    (void)hipFree(s->d_queue);
+    s->d_queue = nullptr;
+    s->queue_cap = 0;
+    const size_t cap = std::min<size_t>(std::max<size_t>(total + total / 2, 4096), 0xffffffffull);
+    if (hipMalloc(&s->d_queue, queue_layout(s->n, cap, nullptr).bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        s->d_queue = nullptr;
+        return MK_ENOMEM;
+    }
+    s->queue_cap = cap;
+    return MK_OK;
+}
+
+// The queue on `st`: group, gather, the ragged launch on the sorted arrays,
+// scatter.  Caller holds s->mu, has the device current and has ordered `st`
+// after the set's last launch; total in [1, 2^32), 1 <= s->n < 2^32.  d_busy:
+// rq_scatter's flag, or null.  A failure before the session kernel leaves the
+// set as it was: the grouping touches no session state.
+int queue_launch(mk_session *s, const uint32_t *d_ids, const int64_t *d_in, size_t total, int32_t *d_out,
+                 uint8_t *d_status, uint32_t *d_steps, uint32_t *d_busy, hipStream_t st)
+{
+    if (s->broken) return MK_EDEVICE;
+    if (int rc = queue_reserve(s, total)) return rc;
+    const QueueBufs q = queue_layout(s->n, s->queue_cap, s->d_queue);
+    const uint32_t n = (uint32_t)s->n, tot = (uint32_t)total;
+    const uint64_t M = total < s->n ? total : s->n;
+    const unsigned blocks = (unsigned)((total + rg::kRgBlock - 1) / rg::kRgBlock);
+    // whatever gets queued reads and writes the scratch: a later launch that grows it must wait
+    bool queued = true;
+    int rc = rg::rg_group(n, d_ids, tot, q.perm, q.sel, q.off, q.m, q.tmp, st);
+    if (rc == MK_OK) {
+        hipLaunchKernelGGL(rg::rq_gather, dim3(blocks), dim3(rg::kRgBlock), 0, st, d_in, (const uint32_t *)q.perm, tot,
+                           q.in);
+        if (hipGetLastError() != hipSuccess) rc = MK_EDEVICE;
+    }
+    if (rc == MK_OK)
+        rc = session_launch(s, q.in, q.out, q.status, d_steps ? q.steps : nullptr, st, 1, false, &queued, nullptr,
+                            q.sel, M, q.off, tot);
+    if (rc == MK_OK) {
+        // off[M] is the number of requests that name a session (req_group.h rg_tail)
+        hipLaunchKernelGGL(rg::rq_scatter, dim3(blocks), dim3(rg::kRgBlock), 0, st, (const uint32_t *)q.perm, d_ids, tot,
+                           (const uint32_t *)(q.off + M), (const int32_t *)q.out, (const uint8_t *)q.status,
+                           (const uint32_t *)q.steps, d_out, d_status, d_steps, d_busy);
+        if (hipGetLastError() != hipSuccess) rc = MK_EDEVICE;
+    }
+    // the scatter is the launch's last kernel: later work on another stream waits for it
+    if (queued) {
+        const int mr = session_mark(s, st);
+        if (rc == MK_OK) rc = mr;
+    }
+    return rc;
+}
+} // namespace
+} // namespace mk
+}
+
+int mk_session_compute_queue_device(mk_session *s, const uint32_t *d_ids, const int64_t *d_in, size_t total,
+                                    int32_t *d_out, uint8_t *d_status, uint32_t *d_steps, void *stream)
+{
+    if (!s || (total && (!d_ids || !d_in || !d_out || !d_status))) return MK_EINVAL;
+    if (total > 0xffffffffull) return MK_EINVAL;
+    if (total == 0) return MK_OK;
+    if (s->n > 0xffffffffull) return MK_ELIMIT;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::DeviceGuard g(s->device);
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    if (int rc = mk::session_wait_last(s, st)) return rc;
+    if (s->n == 0) { // no id names a session
+        if (s->broken) return MK_EDEVICE;
+        if (hipMemsetAsync(d_out, 0, total * 4, st) != hipSuccess ||
+            hipMemsetAsync(d_status, 0, total, st) != hipSuccess ||
+            (d_steps && hipMemsetAsync(d_steps, 0, total * 4, st) != hipSuccess))
+            return MK_EDEVICE;
+        return MK_OK;
+    }
+    return mk::queue_launch(s, d_ids, d_in, total, d_out, d_status, d_steps, nullptr, st);
+}
+
+int mk_session_compute_queue(mk_session *s, const uint32_t *ids, const int64_t *in, size_t total, int32_t *out,
+                             uint8_t *status, uint32_t *steps)
+{
+    if (!s || (total && (!ids || !in || !out || !status))) return MK_EINVAL;
+    if (total > 0xffffffffull) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    for (size_t j = 0; j < total; j++)
+        if (ids[j] >= s->n) return MK_EINVAL;
+    if (total == 0) return MK_OK;
+    if (s->n > 0xffffffffull) return MK_ELIMIT;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    // the staging holds in, out, steps, status, ids and the busy flag
+    const size_t c = total;
+    const size_t a8 = mk::al256(c * 8), a4 = mk::al256(c * 4), a1 = mk::al256(c);
+    const size_t o_ids = a8 + a4 + a4 + a1, o_busy = o_ids + a4;
+    if (int rc = mk::session_stage(s, o_busy + 256)) return rc;
+    char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
+    int64_t *din = (int64_t *)b;
+    int32_t *dout = (int32_t *)(b + a8);
+    uint32_t *dsteps = (uint32_t *)(b + a8 + a4);
+    uint8_t *dst = (uint8_t *)(b + a8 + a4 + a4);
+    uint32_t *dids = (uint32_t *)(b + o_ids), *dbusy = (uint32_t *)(b + o_busy);
+    memcpy(hb, in, c * 8);
+    memcpy(hb + o_ids, ids, c * 4);
+    if (hipMemcpyAsync(din, hb, c * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipMemcpyAsync(dids, hb + o_ids, c * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipMemsetAsync(dbusy, 0, 4, s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    if (int rc = mk::queue_launch(s, dids, din, total, dout, dst, steps ? dsteps : nullptr, dbusy, s->stream)) return rc;
+    if (hipMemcpyAsync(hb + a8, dout, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipMemcpyAsync(hb + a8 + a4 + a4, dst, c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipMemcpyAsync(hb + o_busy, dbusy, 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    if (steps && hipMemcpyAsync(hb + a8 + a4, dsteps, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
+    memcpy(out, hb + a8, c * 4);
+    memcpy(status, hb + a8 + a4 + a4, c);
+    if (steps) memcpy(steps, hb + a8 + a4, c * 4);
+    // the first request of a session that had a call open when this launch began did nothing
+    uint32_t busy;
+    memcpy(&busy, hb + o_busy, 4);
+    return busy ? MK_EBUSY : MK_OK;
 }
 
 int mk_session_cancel_indexed(mk_session *s, const uint32_t *sel, size_t m)

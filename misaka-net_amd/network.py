@@ -559,6 +559,67 @@ class SessionSet:
                                                          status_ptr, steps_ptr, stream),
                 "mk_session_compute_ragged_device")
 
+    def _queue(self, ids, values):
+        """A request queue as the C ABI takes it (uint32 ids, every one < n,
+        int64 values of the same length); ValueError names the first offending
+        position."""
+        raw = ids if isinstance(ids, np.ndarray) else list(ids)
+        a = np.asarray(raw).reshape(-1)
+        if a.size and a.dtype.kind not in "iu":
+            each = list(a) if isinstance(raw, np.ndarray) else raw
+            t = next((i for i, x in enumerate(each) if not isinstance(x, (int, np.integer)) or
+                      isinstance(x, (bool, np.bool_))), 0)
+            raise ValueError(f"ids position {t}: {each[t]!r} is not an integer")
+        a = a.astype(np.int64) if a.size and a.dtype != np.uint64 else a
+        if a.size == 0:
+            a = np.zeros(0, np.int64)
+        bad = (a < 0) | (a >= self.n)
+        if bad.any():
+            t = int(np.argmax(bad))
+            raise ValueError(f"ids position {t}: {a[t]} is not an instance (n = {self.n})")
+        v = np.asarray(values, dtype=np.int64).reshape(-1)
+        if v.size != a.size:
+            t = min(v.size, a.size)
+            raise ValueError(f"ids position {t}: {a.size} ids for {v.size} values (len(ids) != len(values))")
+        if a.size >= 1 << 32:
+            raise ValueError(f"ids position {(1 << 32) - 1}: 2^32 requests or more")
+        return np.ascontiguousarray(a.astype(np.uint32)), np.ascontiguousarray(v)
+
+    def compute_queue(self, ids, values, *, steps=True, busy_ok=False) -> BatchResult:
+        """A request queue in arrival order in one launch: request j is one
+        /compute call with ``values[j]`` on instance ``ids[j]`` -- any order,
+        repeats allowed -- and the results come back in that same order,
+        exactly as if the requests had been served one at a time
+        (mk_session_compute_queue).  The grouping by instance runs on the GPU.
+        The requests of one instance follow the rules of a burst
+        (:meth:`compute_ragged`); an instance with no request is not touched.
+        MkError(MK_EBUSY) unless ``busy_ok`` when the first request of an
+        instance found a call open."""
+        q, v = self._queue(ids, values)
+        total = q.size
+        out = np.zeros(total, np.int32)
+        st = np.zeros(total, np.uint8)
+        sp = np.zeros(total, np.uint32) if steps else None
+        if total:
+            rc = N.lib().mk_session_compute_queue(
+                self._h, q.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), total,
+                out.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p),
+                sp.ctypes.data_as(C.c_void_p) if sp is not None else None)
+            if not (busy_ok and rc == N.MK_EBUSY):
+                N.check(rc, "mk_session_compute_queue")
+        return BatchResult(out, st, sp)
+
+    def compute_queue_device(self, ids_ptr, in_ptr, total, out_ptr, status_ptr, steps_ptr=None, *, stream=None):
+        """A request queue on device arrays of ``total`` words each,
+        asynchronous on ``stream`` (mk_session_compute_queue_device).  The
+        ids (uint32) are taken on trust; a request whose id is ``>= n``
+        touches no instance and reports 0 / 0 / 0."""
+        if not 0 <= total < 1 << 32:
+            raise ValueError(f"total = {total} outside [0, 2^32)")
+        N.check(N.lib().mk_session_compute_queue_device(self._h, ids_ptr, in_ptr, total, out_ptr, status_ptr,
+                                                        steps_ptr, stream),
+                "mk_session_compute_queue_device")
+
     def reset(self, *, index=None):
         """/reset (master.go:126-143): every instance back to its initial
         state; with ``index``, the listed instances only."""
@@ -742,3 +803,27 @@ def valu_probe_device(blocks, iters, *, device=0, stream=None) -> int:
     ops = C.c_uint64()
     N.check(N.lib().mk_valu_probe_device(device, blocks, iters, C.byref(ops), stream))
     return ops.value
+
+
+def group_requests_tmp_bytes(n, total) -> int:
+    """Bytes of device scratch :func:`group_requests_device` needs for
+    ``total`` requests on ``n`` sessions (mk_requests_group_tmp_bytes)."""
+    b = C.c_size_t()
+    if not 0 <= n < 1 << 32 or total < 0:
+        raise ValueError(f"n = {n}, total = {total}")
+    N.check(N.lib().mk_requests_group_tmp_bytes(n, total, C.byref(b)), "mk_requests_group_tmp_bytes")
+    return b.value
+
+
+def group_requests_device(n, ids_ptr, total, perm_ptr, sel_ptr, off_ptr, m_ptr, tmp_ptr, tmp_bytes, *, device=0,
+                          stream=None):
+    """Group a request queue on the GPU, asynchronous on ``stream``
+    (mk_requests_group_device): from ``total`` uint32 ids in arrival order,
+    the stable order ``perm`` of ``min(id, n)``, the distinct ids below ``n``
+    (``sel``, ``min(total, n)`` words, padded with 0xffffffff), where each
+    one's requests start in that order (``off``, one word more, padded with
+    the number of valid requests) and their number (``m``, one word)."""
+    if not 0 <= n < 1 << 32 or total < 0:
+        raise ValueError(f"n = {n}, total = {total}")
+    N.check(N.lib().mk_requests_group_device(device, n, ids_ptr, total, perm_ptr, sel_ptr, off_ptr, m_ptr, tmp_ptr,
+                                             tmp_bytes, stream), "mk_requests_group_device")
