@@ -69,6 +69,7 @@ extern char **environ;
 #define MK_HD __host__ __device__
 #include "sess_convert.h"
 #include "sess_record.h"
+#include "sess_stage.h"
 #include "req_group.h"
 
 namespace mk {
@@ -3745,36 +3746,60 @@ struct SessKSel {
     uint32_t total;
 };
 
+// What one launch of a set's session kernels works on: device arrays, and which
+// sessions make how many calls.  With `sel` the launch is a selected one: m
+// threads, thread t on session sel[t], the I/O arrays [ncalls][m]; the grids
+// cover m, not n.  With `off` it is selected and ragged
+// (mk_session_compute_ragged): entry t makes off[t+1] - off[t] calls, the I/O
+// arrays are compact, of length total, ncalls is not used, and a null sel
+// lists every session.
+struct SessCall {
+    const int64_t *in = nullptr;
+    int32_t *out = nullptr;
+    uint8_t *status = nullptr;
+    uint32_t *steps = nullptr;
+    uint32_t ncalls = 1;
+    bool resume = false;
+    const uint32_t *sel = nullptr;
+    uint64_t m = 0;
+    const uint32_t *off = nullptr;
+    uint32_t total = 0;
+    // the four I/O arrays, in the order every form of the ABI lists them
+    static SessCall io(const int64_t *in, int32_t *out, uint8_t *status, uint32_t *steps)
+    {
+        SessCall c;
+        c.in = in;
+        c.out = out;
+        c.status = status;
+        c.steps = steps;
+        return c;
+    }
+};
+
 // *queued (when given) is set once a kernel has been queued on `stream`, so
 // that a caller whose launch fails part way still orders later work after it.
 // `done` (when given) is recorded by the launch's last kernel itself, as its
 // completion event (hipExtModuleLaunchKernel / hipExtLaunchKernel stop
 // event), instead of by a separate hipEventRecord after it: that marker cost
 // ~3 us of stream time per call (round 6, profiles/r08_sessions_ab.txt).
-// With d_sel the launch is a selected one: m threads, thread t on session
-// d_sel[t], the I/O arrays [ncalls][m]; the grids cover m, not n.
-// With d_off the launch is selected and ragged (mk_session_compute_ragged):
-// entry t makes d_off[t+1] - d_off[t] calls, the I/O arrays are compact, of
-// length total, ncalls is not used, and a null d_sel lists every session.
-int session_launch(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *d_status, uint32_t *d_steps,
-                   hipStream_t stream, uint32_t ncalls = 1, bool resume = false, bool *queued = nullptr,
-                   hipEvent_t done = nullptr, const uint32_t *d_sel = nullptr, uint64_t m = 0,
-                   const uint32_t *d_off = nullptr, uint32_t total = 0)
+int session_launch(mk_session *s, const SessCall &c, hipStream_t stream, bool *queued = nullptr,
+                   hipEvent_t done = nullptr)
 {
     if (s->broken) return MK_EDEVICE;
-    const bool sel = d_sel || d_off;
-    if (s->n == 0 || ncalls == 0 || (sel && m == 0) || (d_off && total == 0)) return MK_OK;
+    const bool resume = c.resume, sel = c.sel || c.off;
+    const uint64_t m = c.m;
+    if (s->n == 0 || c.ncalls == 0 || (sel && m == 0) || (c.off && c.total == 0)) return MK_OK;
     SessParams p = s->p;
-    p.sel = d_sel;
+    p.sel = c.sel;
     p.m = m;
-    p.off = d_off;
-    p.total = total;
-    p.ncalls = ncalls;
+    p.off = c.off;
+    p.total = c.total;
+    p.ncalls = c.ncalls;
     p.resume = resume ? 1u : 0u;
-    p.in = d_in;
-    p.out = d_out;
-    p.status = d_status;
-    p.steps = d_steps;
+    p.in = c.in;
+    p.out = c.out;
+    p.status = c.status;
+    p.steps = c.steps;
     const Insn *code = s->h->dev[s->device].d_code;
     const size_t lds = (size_t)(s->nprog * 4 + s->nstack) * kBlock * 4;
     const uint64_t blocks = ((sel ? m : (uint64_t)s->n) + kBlock - 1) / kBlock;
@@ -3785,9 +3810,9 @@ int session_launch(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *
     if (s->native && !resume) {
         if (++s->epoch == 0) s->epoch = 1; // sflags[0] starts at 0: "no hand-off yet"
         // 1. the native kernel: every session it holds, every call of the burst
-        SessK k{s->n, ncalls, p.budget, d_in, d_out, d_status, d_steps, s->nsb, s->regs, s->slots,
+        SessK k{s->n, c.ncalls, p.budget, c.in, c.out, c.status, c.steps, s->nsb, s->regs, s->slots,
                 s->hand_sb, s->hand_steps, s->hand_call, s->sflags, s->epoch};
-        SessKSel ks{k, d_sel, m, d_off, total};
+        SessKSel ks{k, c.sel, m, c.off, c.total};
         void *kargs[] = {sel ? (void *)&ks : (void *)&k};
         // the native kernel is the launch's last when the interpreter pass is
         // skipped (below: no call can reach the budget)
@@ -3853,29 +3878,28 @@ int session_native(mk_session *s)
     std::vector<SessSrcDev> rec;
     build_sess_map(P, s->nprog, s->nstack, hdr, rec);
     const size_t N = s->n ? s->n : 1;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t sz[] = {al(N * 4), al((size_t)P.nregs * N * 8), al((size_t)std::max<uint32_t>(P.nslots, 1) * N * 4),
-                         al(N * 4), al(N * 4), al(N * 4), al(16), al(hdr.size() * sizeof(SessMapHdr)),
-                         al(rec.size() * sizeof(SessSrcDev)), al(std::max<size_t>(P.dyn_base.size(), 1) * 8),
-                         al((hdr.size() + 31) / 32 * 4 + 4)};
-    size_t total = 0;
-    for (size_t b : sz) total += b;
+    size_t lane_bytes = 0;
+    // first over nothing, for the size, then over the allocation
+    auto carve = [&](void *base) {
+        Carver k(base);
+        s->nsb = k.take<uint32_t>(N);
+        s->regs = k.take<int64_t>((size_t)P.nregs * N);
+        s->slots = k.take<int32_t>((size_t)std::max<uint32_t>(P.nslots, 1) * N);
+        s->hand_sb = k.take<uint32_t>(N);
+        s->hand_steps = k.take<uint32_t>(N);
+        s->hand_call = k.take<uint32_t>(N);
+        s->sflags = k.take<uint32_t>(4);
+        lane_bytes = k.at; // the lane state: what a reset clears
+        s->hdr = k.take<SessMapHdr>(hdr.size());
+        s->rec = k.take<SessSrcDev>(rec.size());
+        s->dyn_base = k.take<int64_t>(std::max<size_t>(P.dyn_base.size(), 1));
+        s->pre = k.take<uint32_t>((hdr.size() + 31) / 32 + 1);
+        return k.at;
+    };
+    const size_t total = carve(nullptr);
     if (hipMalloc(&s->d_native, total) != hipSuccess) return MK_ENOMEM;
     s->native_bytes = total;
-    char *b = (char *)s->d_native;
-    size_t off = 0;
-    auto take = [&](size_t i) { char *q = b + off; off += sz[i]; return q; };
-    s->nsb = (uint32_t *)take(0);
-    s->regs = (int64_t *)take(1);
-    s->slots = (int32_t *)take(2);
-    s->hand_sb = (uint32_t *)take(3);
-    s->hand_steps = (uint32_t *)take(4);
-    s->hand_call = (uint32_t *)take(5);
-    s->sflags = (uint32_t *)take(6);
-    s->hdr = (SessMapHdr *)take(7);
-    s->rec = (SessSrcDev *)take(8);
-    s->dyn_base = (int64_t *)take(9);
-    s->pre = (uint32_t *)take(10);
+    carve(s->d_native);
     s->nsbk = (uint32_t)hdr.size();
     s->h_pre.assign((hdr.size() + 31) / 32 + 1, 0u);
     for (size_t k = 0; k < hdr.size(); k++)
@@ -3895,7 +3919,7 @@ int session_native(mk_session *s)
     s->h_hdr = std::move(hdr);
     s->h_rec = std::move(rec);
     s->h_dyn_base = P.dyn_base;
-    s->native_bytes = sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + sz[5] + sz[6]; // the lane state: what a reset clears
+    s->native_bytes = lane_bytes;
     s->native = true;
     s->call_steps = jit_session_max_call_steps(P, h->jit_lim);
     s->p.nsb = s->nsb;
@@ -3915,6 +3939,460 @@ int session_native(mk_session *s)
                                                      : std::string(" launches=2");
     return MK_OK;
 }
+
+// Orders work about to be queued on `to` after the session's last launch on
+// a caller stream: a device-side wait on the event recorded after that
+// launch, skipped when `to` is that same stream (stream order already holds;
+// the two-way event hand-off per call had cost ~20 us of stream latency per
+// launch, profiles/r06s_sessions_stream_order.txt).
+int session_wait_last(mk_session *s, hipStream_t to)
+{
+    if (!s->last || s->last == to) return MK_OK;
+    if (hipStreamWaitEvent(to, s->order, 0) != hipSuccess) return MK_EDEVICE;
+    if (to == s->stream) s->last = nullptr; // s->stream now follows every launch so far
+    return MK_OK;
+}
+
+// After a launch on `st` (a caller's or the session's own stream): work queued
+// later on any other stream waits on this.
+int session_mark(mk_session *s, hipStream_t st)
+{
+    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
+    if (hipEventRecord(s->order, st) != hipSuccess) return MK_EDEVICE;
+    s->last = st;
+    return MK_OK;
+}
+
+// The stream of a device form (a caller's, or the set's own for null), ordered
+// after the set's last launch.  The session state is ordered across streams
+// device-side, with no host synchronisation: this launch after the previous
+// one (a wait only when that ran on another stream), and the session's own
+// stream's later work (reset, host calls) after this one.
+int session_enter(mk_session *s, void *stream, hipStream_t *st)
+{
+    *st = stream ? (hipStream_t)stream : s->stream;
+    return session_wait_last(s, *st);
+}
+
+// The envelope of a device form: launch(st, &queued, done) queues the form's
+// kernels on its stream, the last of them recording `done` (s->order, what
+// session_mark records) as its completion event.  A launch that fails after
+// it queued something -- the native kernel may be running on `st` -- is still
+// marked: reset and teardown must wait for it.  Caller holds s->mu, under
+// which it has also made the checks that read the set's state.
+template <class Launch>
+int session_on_stream(mk_session *s, void *stream, Launch launch)
+{
+    DeviceGuard g(s->device);
+    hipStream_t st;
+    if (int rc = session_enter(s, stream, &st)) return rc;
+    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
+    bool queued = false;
+    if (int rc = launch(st, &queued, s->order)) {
+        if (queued) (void)session_mark(s, st);
+        return rc;
+    }
+    s->last = st;
+    return MK_OK;
+}
+
+// One element of session state (device), read or written synchronously on
+// the session's stream (ordered after its launches).  Caller holds s->mu.
+template <class T>
+int sget(mk_session *s, const T *dev, T &v)
+{
+    if (int rc = session_wait_last(s, s->stream)) return rc;
+    if (hipMemcpyAsync(&v, dev, sizeof(T), hipMemcpyDeviceToHost, s->stream) != hipSuccess) return MK_EDEVICE;
+    return hipStreamSynchronize(s->stream) == hipSuccess ? MK_OK : MK_EDEVICE;
+}
+template <class T>
+int sput(mk_session *s, T *dev, const T &v)
+{
+    if (int rc = session_wait_last(s, s->stream)) return rc;
+    if (hipMemcpyAsync(dev, &v, sizeof(T), hipMemcpyHostToDevice, s->stream) != hipSuccess) return MK_EDEVICE;
+    return hipStreamSynchronize(s->stream) == hipSuccess ? MK_OK : MK_EDEVICE;
+}
+
+// The host forms' check of an index list: at most n entries, strictly
+// increasing (so no two threads of a launch share a session), every one < n.
+bool sel_valid(const mk_session *s, const uint32_t *sel, size_t m)
+{
+    if (m > s->n || (m && !sel)) return false;
+    for (size_t t = 0; t < m; t++)
+        if (sel[t] >= s->n || (t && sel[t] <= sel[t - 1])) return false;
+    return true;
+}
+
+// The host-API staging (d_stage and its pinned mirror) with room for `need`
+// bytes.  Caller holds s->mu.
+int session_stage(mk_session *s, size_t need)
+{
+    if (need <= s->stage_bytes) return MK_OK;
+    (void)hipFree(s->d_stage);
+    (void)hipHostFree(s->h_stage);
+    s->d_stage = s->h_stage = nullptr;
+    s->stage_bytes = 0;
+    if (hipMalloc(&s->d_stage, need) != hipSuccess) return MK_ENOMEM;
+    if (hipHostMalloc(&s->h_stage, need, hipHostMallocDefault) != hipSuccess) return MK_ENOMEM;
+    s->stage_bytes = need;
+    return MK_OK;
+}
+
+// What a host form hands over: its host arrays of c words each (a null `in`
+// is a resume, the kernel ignores the inputs) and the extras it stages
+// (sess_stage.h stage_layout): sel[m], off[m + 1], ids[c], the 4-byte flag.
+struct HostIO {
+    size_t c = 0;
+    const int64_t *in = nullptr;
+    int32_t *out = nullptr;
+    uint8_t *status = nullptr;
+    uint32_t *steps = nullptr;
+    size_t m = 0;
+    const uint32_t *sel = nullptr, *off = nullptr, *ids = nullptr;
+    uint32_t *flag = nullptr; // receives the device flag, cleared before the launch
+    static HostIO of(size_t c, const int64_t *in, int32_t *out, uint8_t *status, uint32_t *steps)
+    {
+        HostIO io;
+        io.c = c;
+        io.in = in;
+        io.out = out;
+        io.status = status;
+        io.steps = steps;
+        return io;
+    }
+};
+
+// The same arrays in the device staging, as launch() gets them; an extra that
+// was not given, and steps when the caller wants none, are null.
+struct StageDev {
+    const int64_t *in;
+    int32_t *out;
+    uint8_t *status;
+    uint32_t *steps;
+    const uint32_t *sel, *off, *ids;
+    uint32_t *flag;
+};
+
+// The round trip of a host form through the staging and its pinned mirror
+// (small bursts are latency-bound: pinned copies avoid the runtime's pageable
+// staging and its extra sync), all on s->stream: one copy up per array given,
+// launch(StageDev), out, status, the flag and steps down, one synchronise.
+// Caller holds s->mu, has the device current and has ordered s->stream after
+// the set's last launch.
+template <class Launch>
+int session_round_trip(mk_session *s, const HostIO &io, Launch launch)
+{
+    const StageLayout L = stage_layout(io.c, io.m, io.sel, io.off, io.ids, io.flag);
+    if (int rc = session_stage(s, L.bytes)) return rc;
+    char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
+    const hipStream_t st = s->stream;
+    auto up = [&](size_t at, size_t bytes) {
+        return hipMemcpyAsync(b + at, hb + at, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
+    };
+    auto down = [&](size_t at, size_t bytes) {
+        return hipMemcpyAsync(hb + at, b + at, bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+    };
+    const size_t c = io.c, m = io.m;
+    if (io.in) memcpy(hb + L.in, io.in, c * 8);
+    else memset(hb + L.in, 0, c * 8);
+    if (io.off) memcpy(hb + L.off, io.off, (m + 1) * 4);
+    if (io.sel) memcpy(hb + L.sel, io.sel, m * 4);
+    if (io.ids) memcpy(hb + L.ids, io.ids, c * 4);
+    if (!up(L.in, c * 8) || (io.off && !up(L.off, (m + 1) * 4)) || (io.sel && !up(L.sel, m * 4)) ||
+        (io.ids && !up(L.ids, c * 4)) || (io.flag && hipMemsetAsync(b + L.flag, 0, 4, st) != hipSuccess))
+        return MK_EDEVICE;
+    auto u32 = [&](const void *given, size_t at) { return given ? (uint32_t *)(b + at) : nullptr; };
+    const StageDev d{(const int64_t *)(b + L.in), (int32_t *)(b + L.out), (uint8_t *)(b + L.status),
+                     u32(io.steps, L.steps), u32(io.sel, L.sel), u32(io.off, L.off), u32(io.ids, L.ids),
+                     u32(io.flag, L.flag)};
+    if (int rc = launch(d)) return rc;
+    if (!down(L.out, c * 4) || !down(L.status, c) || (io.flag && !down(L.flag, 4)) ||
+        (io.steps && !down(L.steps, c * 4)))
+        return MK_EDEVICE;
+    if (hipStreamSynchronize(st) != hipSuccess) return MK_EDEVICE;
+    memcpy(io.out, hb + L.out, c * 4);
+    memcpy(io.status, hb + L.status, c);
+    if (io.steps) memcpy(io.steps, hb + L.steps, c * 4);
+    if (io.flag) memcpy(io.flag, hb + L.flag, 4);
+    return MK_OK;
+}
+
+// The one host burst behind the plain, indexed and ragged host forms: entry t
+// of io.m is session sel[t] (t itself for a null list) and makes ncalls
+// calls, or, with off, off[t + 1] - off[t] of them; io.c is the number of
+// calls in all.  A plain call on every session is the null list without off.
+// MK_EBUSY, after the results have been copied out, when an entry with a call
+// to make had one open as this launch began: it did nothing, and its first
+// call says so (MK_ST_CALL_OPEN; resume or cancel that call first).  Never
+// for a resume (a null io.in).  Caller holds s->mu and has checked the lists;
+// io.c > 0.
+int session_host_burst(mk_session *s, const HostIO &io, uint32_t ncalls)
+{
+    DeviceGuard g(s->device);
+    if (int rc = session_wait_last(s, s->stream)) return rc;
+    const bool resume = !io.in;
+    int rc = session_round_trip(s, io, [&](const StageDev &d) {
+        SessCall k = SessCall::io(d.in, d.out, d.status, d.steps);
+        k.ncalls = ncalls;
+        k.resume = resume;
+        if (io.sel || io.off) {
+            k.sel = d.sel;
+            k.m = io.m;
+            k.off = d.off;
+            k.total = io.off ? (uint32_t)io.c : 0;
+        }
+        return session_launch(s, k, s->stream);
+    });
+    if (rc || resume) return rc;
+    for (size_t t = 0; t < io.m; t++)
+        if (io.off ? io.off[t + 1] > io.off[t] && io.status[io.off[t]] == MK_ST_CALL_OPEN
+                   : io.status[t] == MK_ST_CALL_OPEN)
+            return MK_EBUSY;
+    return MK_OK;
+}
+
+// The list on the device, in the staging (at its start: the layout of no I/O
+// words), for the small indexed kernels; *d_sel is null for a null list.
+// `extra`, when given, asks for room for *extra bytes behind the list and
+// receives their offset.  Caller holds s->mu and has ordered s->stream after
+// the set's last launch.
+int session_stage_sel(mk_session *s, const uint32_t *sel, size_t m, size_t *extra, uint32_t **d_sel)
+{
+    const StageLayout L = stage_layout(0, m, sel, false, false, false);
+    if (int rc = session_stage(s, L.bytes + (extra ? Carver::al(*extra) : 0))) return rc;
+    if (extra) *extra = L.bytes;
+    *d_sel = nullptr;
+    if (!sel) return MK_OK;
+    memcpy((char *)s->h_stage + L.sel, sel, m * 4);
+    if (hipMemcpyAsync((char *)s->d_stage + L.sel, (char *)s->h_stage + L.sel, m * 4, hipMemcpyHostToDevice,
+                       s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    *d_sel = (uint32_t *)((char *)s->d_stage + L.sel);
+    return MK_OK;
+}
+
+// Grid of the small indexed kernels: one thread per listed session.
+bool sel_grid(size_t m, unsigned *blocks)
+{
+    const uint64_t b = ((uint64_t)m + kBlock - 1) / kBlock;
+    if (b * kBlock > 0xffffffffull) return false;
+    *blocks = (unsigned)b;
+    return true;
+}
+
+// The queue scratch of a set, for `total` requests.
+struct QueueBufs {
+    void *tmp;
+    uint32_t *perm, *sel, *off, *m;
+    int64_t *in;
+    int32_t *out;
+    uint32_t *steps;
+    uint8_t *status;
+    size_t bytes;
+};
+
+QueueBufs queue_layout(size_t n, size_t total, void *base)
+{
+    const size_t M = total < n ? total : n;
+    Carver k(base);
+    QueueBufs q{};
+    q.tmp = k.take<char>(rg::rg_tmp_layout(total).bytes);
+    q.perm = k.take<uint32_t>(total);
+    q.sel = k.take<uint32_t>(M);
+    q.off = k.take<uint32_t>(M + 1);
+    q.m = k.take<uint32_t>(1);
+    q.in = k.take<int64_t>(total);
+    q.out = k.take<int32_t>(total);
+    q.steps = k.take<uint32_t>(total);
+    q.status = k.take<uint8_t>(total);
+    q.bytes = k.at;
+    return q;
+}
+
+// Room for `total` requests.  Growing waits for the set's last launch -- it
+// may be reading the old scratch -- then frees and reallocates; a failed
+// allocation leaves the set without a scratch and usable.  Caller holds s->mu.
+int queue_reserve(mk_session *s, size_t total)
+{
+    if (total <= s->queue_cap) return MK_OK;
+    if (s->last && s->order && hipEventSynchronize(s->order) != hipSuccess) return MK_EDEVICE;
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
+    (void)hipFree(s->d_queue);
+    s->d_queue = nullptr;
+    s->queue_cap = 0;
+    const size_t cap = std::min<size_t>(std::max<size_t>(total + total / 2, 4096), 0xffffffffull);
+    if (hipMalloc(&s->d_queue, queue_layout(s->n, cap, nullptr).bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        s->d_queue = nullptr;
+        return MK_ENOMEM;
+    }
+    s->queue_cap = cap;
+    return MK_OK;
+}
+
+// The queue on `st`: group, gather, the ragged launch on the sorted arrays,
+// scatter.  Caller holds s->mu, has the device current and has ordered `st`
+// after the set's last launch; total in [1, 2^32), 1 <= s->n < 2^32.  d_busy:
+// rq_scatter's flag, or null.  A failure before the session kernel leaves the
+// set as it was: the grouping touches no session state.
+int queue_launch(mk_session *s, const uint32_t *d_ids, const int64_t *d_in, size_t total, int32_t *d_out,
+                 uint8_t *d_status, uint32_t *d_steps, uint32_t *d_busy, hipStream_t st)
+{
+    if (s->broken) return MK_EDEVICE;
+    if (int rc = queue_reserve(s, total)) return rc;
+    const QueueBufs q = queue_layout(s->n, s->queue_cap, s->d_queue);
+    const uint32_t n = (uint32_t)s->n, tot = (uint32_t)total;
+    const uint64_t M = total < s->n ? total : s->n;
+    const unsigned blocks = (unsigned)((total + rg::kRgBlock - 1) / rg::kRgBlock);
+    // whatever gets queued reads and writes the scratch: a later launch that grows it must wait
+    bool queued = true;
+    int rc = rg::rg_group(n, d_ids, tot, q.perm, q.sel, q.off, q.m, q.tmp, st);
+    if (rc == MK_OK) {
+        hipLaunchKernelGGL(rg::rq_gather, dim3(blocks), dim3(rg::kRgBlock), 0, st, d_in, (const uint32_t *)q.perm, tot,
+                           q.in);
+        if (hipGetLastError() != hipSuccess) rc = MK_EDEVICE;
+    }
+    if (rc == MK_OK) {
+        SessCall k = SessCall::io(q.in, q.out, q.status, d_steps ? q.steps : nullptr);
+        k.sel = q.sel;
+        k.m = M;
+        k.off = q.off;
+        k.total = tot;
+        rc = session_launch(s, k, st, &queued);
+    }
+    if (rc == MK_OK) {
+        // off[M] is the number of requests that name a session (req_group.h rg_tail)
+        hipLaunchKernelGGL(rg::rq_scatter, dim3(blocks), dim3(rg::kRgBlock), 0, st, (const uint32_t *)q.perm, d_ids, tot,
+                           (const uint32_t *)(q.off + M), (const int32_t *)q.out, (const uint8_t *)q.status,
+                           (const uint32_t *)q.steps, d_out, d_status, d_steps, d_busy);
+        if (hipGetLastError() != hipSuccess) rc = MK_EDEVICE;
+    }
+    // the scatter is the launch's last kernel: later work on another stream waits for it
+    if (queued) {
+        const int mr = session_mark(s, st);
+        if (rc == MK_OK) rc = mr;
+    }
+    return rc;
+}
+
+// What identifies a network to a record: FNV-1a over the node names, their
+// kinds and the lowered bytecode.
+uint64_t net_hash(const Network &N)
+{
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&](const void *p, size_t k) {
+        for (size_t i = 0; i < k; i++) h = (h ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
+    };
+    auto str = [&](const std::string &x, int kind) {
+        mix(x.c_str(), x.size() + 1);
+        mix(&kind, sizeof kind);
+    };
+    for (const std::string &x : N.prog_names) str(x, NK_PROGRAM);
+    for (const std::string &x : N.stack_names) str(x, NK_STACK);
+    for (size_t i = 0; i < N.remote_names.size(); i++) str(N.remote_names[i], N.remote_kinds[i]);
+    for (size_t k = 0; k < N.base.size(); k++) {
+        mix(&N.base[k], 4);
+        mix(&N.len[k], 4);
+    }
+    for (const Insn &I : N.code) {
+        const int64_t w[6] = {I.op, I.src, I.dst, I.arg, I.imm, 0};
+        mix(w, sizeof w);
+    }
+    return h;
+}
+
+SessRecShape session_shape(const mk_session *s) { return SessRecShape{s->nprog, s->nstack, s->cap, s->nregs, s->nslots}; }
+
+void session_layout(const mk_session *s, mk_session_layout *out)
+{
+    const SessRecShape L = session_shape(s);
+    *out = mk_session_layout{};
+    out->magic = kSessRecMagic;
+    out->version = kSessRecVersion;
+    out->net_hash = s->net_hash;
+    out->native_hash = s->native ? s->native_hash : 0;
+    out->nprog = (uint32_t)s->nprog;
+    out->nstack = (uint32_t)s->nstack;
+    out->stack_cap = s->cap;
+    out->native_rows = s->native ? L.native_rows() : 0u;
+    out->rows = L.canon_rows() + out->native_rows;
+}
+
+// A block's layout against the set's: the canonical part must be this
+// network's at this stack_cap, the block's row count its own sections'.
+bool layout_fits(const mk_session *s, const mk_session_layout *from)
+{
+    mk_session_layout own;
+    session_layout(s, &own);
+    return from->magic == own.magic && from->version == own.version && from->net_hash == own.net_hash &&
+           from->nprog == own.nprog && from->nstack == own.nstack && from->stack_cap == own.stack_cap &&
+           from->rows == own.rows - own.native_rows + from->native_rows && from->rows >= from->native_rows;
+}
+
+// the block's native section is this set's own
+bool layout_native(const mk_session *s, const mk_session_layout *from)
+{
+    return s->native && from->native_hash != 0 && from->native_hash == s->native_hash &&
+           from->native_rows == session_shape(s).native_rows();
+}
+
+SessSnapK session_snapk(const mk_session *s, bool nat_ok)
+{
+    SessSnapK q{};
+    if (s->native)
+        q = SessSnapK{s->nsb, s->hand_sb, s->hand_steps, s->hand_call, s->sflags, s->regs, s->slots, s->nregs,
+                      s->nslots, s->hdr, s->rec, s->dyn_base, s->pre, s->nsbk, nat_ok ? 1u : 0u};
+    return q;
+}
+
+// Grid of the two kernels: one thread per entry, the tall row groups over y.
+dim3 snap_grid(const mk_session *s, unsigned blocks)
+{
+    const uint64_t tall = std::max<uint64_t>(
+        {(uint64_t)s->nstack * s->cap, s->native ? 2ull * s->nregs : 0ull, s->native ? (uint64_t)s->nslots : 0ull, 1ull});
+    return dim3(blocks, (unsigned)std::min<uint64_t>(tall, 64));
+}
+
+// Queues the export of m entries (sessions d_sel[t], or first + t) into the
+// device block d_rec on `st`; `done` as in session_launch.
+int snapshot_launch(mk_session *s, const uint32_t *d_sel, uint64_t first, uint64_t m, uint32_t *d_rec, hipStream_t st,
+                    hipEvent_t done)
+{
+    unsigned blocks;
+    if (!sel_grid(m, &blocks)) return MK_ELIMIT;
+    SessParams p = s->p;
+    SessSnapK q = session_snapk(s, false);
+    void *args[] = {(void *)&p, (void *)&q, (void *)&d_sel, (void *)&first, (void *)&m, (void *)&d_rec};
+    return hipExtLaunchKernel(reinterpret_cast<void *>(&tis_session_export_sel), snap_grid(s, blocks), dim3(kBlock), args,
+                              0, st, nullptr, done, 0) == hipSuccess
+               ? MK_OK
+               : MK_EDEVICE;
+}
+
+// may_hold: a record of the block may be restored from its canonical part.
+int restore_launch(mk_session *s, const uint32_t *d_sel, uint64_t first, uint64_t m, bool nat_ok, bool may_hold,
+                   const uint32_t *d_rec, uint64_t mcols, const uint32_t *d_col, hipStream_t st, hipEvent_t done)
+{
+    unsigned blocks;
+    if (!sel_grid(m, &blocks)) return MK_ELIMIT;
+    SessParams p = s->p;
+    SessSnapK q = session_snapk(s, nat_ok);
+    void *args[] = {(void *)&p,     (void *)&q,     (void *)&d_sel, (void *)&first,
+                    (void *)&m,     (void *)&d_rec, (void *)&mcols, (void *)&d_col};
+    if (hipExtLaunchKernel(reinterpret_cast<void *>(&tis_session_restore_sel), snap_grid(s, blocks), dim3(kBlock), args,
+                           0, st, nullptr, done, 0) != hipSuccess)
+        return MK_EDEVICE;
+    if (may_hold) s->interp_may_hold = true; // a canonical restore hands its session to the interpreter
+    return MK_OK;
+}
+
+// Entries of a host form's staging chunk: at most 64 MiB of rows.
+size_t snap_chunk(uint32_t rows, size_t m) { return std::min<size_t>(m, std::max<size_t>(1, ((size_t)64 << 20) / ((size_t)rows * 4))); }
+
+struct DevBlock {
+    void *p = nullptr;
+    ~DevBlock() { (void)hipFree(p); }
+};
 
 void set_err(char *err, size_t len, const std::string &s)
 {
@@ -4005,7 +4483,7 @@ int mk_compute_batch(mk_net *h, const int64_t *in, size_t n, int32_t *out, uint8
     // runtime's own pipelined staging moves more bytes per second than one
     // host thread copying into pinned memory (C2, 16M lanes: 9.7 ms per call
     // pageable vs 13.2 ms through a single-threaded pinned double buffer).
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    auto plain = [](size_t m) { return mk::stage_layout(m, 0, false, false, false, false); }; // in, out, steps, status
     for (auto &j : jobs) {
         int rc = mk::ensure_device(h, j.d);
         if (rc) return rc;
@@ -4013,8 +4491,8 @@ int mk_compute_batch(mk_net *h, const int64_t *in, size_t n, int32_t *out, uint8
         mk::DeviceGuard g(j.d);
         const size_t m = j.hi - j.lo;
         const bool pinned = m <= h->host_chunk;
-        const size_t a8 = al(m * 8), a4 = al(m * 4), a1 = al(m);
-        const size_t need = a8 + a4 + a4 + a1; // in, out, steps, status
+        const mk::StageLayout L = plain(m);
+        const size_t need = L.bytes;
         if (need > c.stage_bytes || (pinned && !c.h_stage)) {
             (void)hipStreamSynchronize(c.stream);
             (void)hipFree(c.d_stage);
@@ -4023,7 +4501,7 @@ int mk_compute_batch(mk_net *h, const int64_t *in, size_t n, int32_t *out, uint8
             c.stage_bytes = 0;
             const size_t sz = std::max(need, c.stage_bytes);
             if (hipMalloc(&c.d_stage, sz) != hipSuccess) return MK_ENOMEM;
-            if (sz <= al(h->host_chunk * 8) + 2 * al(h->host_chunk * 4) + al(h->host_chunk) &&
+            if (sz <= plain(h->host_chunk).bytes &&
                 hipHostMalloc(&c.h_stage, sz, hipHostMallocDefault) != hipSuccess)
                 return MK_ENOMEM;
             c.stage_bytes = sz;
@@ -4039,16 +4517,16 @@ int mk_compute_batch(mk_net *h, const int64_t *in, size_t n, int32_t *out, uint8
         mk_input mi{};
         mi.kind = MK_IN_I64;
         mi.data = db;
-        rc = mk::launch_locked(h, j.d, &mi, m, (int32_t *)(db + a8), (uint8_t *)(db + a8 + a4 + a4),
-                               steps ? (uint32_t *)(db + a8 + a4) : nullptr, nullptr, opts, c.stream);
+        rc = mk::launch_locked(h, j.d, &mi, m, (int32_t *)(db + L.out), (uint8_t *)(db + L.status),
+                               steps ? (uint32_t *)(db + L.steps) : nullptr, nullptr, opts, c.stream);
         if (rc) return rc;
-        char *o = hb ? hb + a8 : (char *)(out + j.lo);
-        char *st = hb ? hb + a8 + a4 + a4 : (char *)(status + j.lo);
-        char *sp = hb ? hb + a8 + a4 : (char *)(steps ? steps + j.lo : nullptr);
-        if (hipMemcpyAsync(o, db + a8, m * 4, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
-            hipMemcpyAsync(st, db + a8 + a4 + a4, m, hipMemcpyDeviceToHost, c.stream) != hipSuccess)
+        char *o = hb ? hb + L.out : (char *)(out + j.lo);
+        char *st = hb ? hb + L.status : (char *)(status + j.lo);
+        char *sp = hb ? hb + L.steps : (char *)(steps ? steps + j.lo : nullptr);
+        if (hipMemcpyAsync(o, db + L.out, m * 4, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+            hipMemcpyAsync(st, db + L.status, m, hipMemcpyDeviceToHost, c.stream) != hipSuccess)
             return MK_EDEVICE;
-        if (steps && hipMemcpyAsync(sp, db + a8 + a4, m * 4, hipMemcpyDeviceToHost, c.stream) != hipSuccess)
+        if (steps && hipMemcpyAsync(sp, db + L.steps, m * 4, hipMemcpyDeviceToHost, c.stream) != hipSuccess)
             return MK_EDEVICE;
     }
     int rc = MK_OK;
@@ -4062,10 +4540,10 @@ int mk_compute_batch(mk_net *h, const int64_t *in, size_t n, int32_t *out, uint8
         const size_t m = j.hi - j.lo;
         if (m <= h->host_chunk && c.h_stage) {
             const char *hb = (const char *)c.h_stage;
-            const size_t a8 = al(m * 8), a4 = al(m * 4);
-            memcpy(out + j.lo, hb + a8, m * 4);
-            if (steps) memcpy(steps + j.lo, hb + a8 + a4, m * 4);
-            memcpy(status + j.lo, hb + a8 + a4 + a4, m);
+            const mk::StageLayout L = plain(m);
+            memcpy(out + j.lo, hb + L.out, m * 4);
+            if (steps) memcpy(steps + j.lo, hb + L.steps, m * 4);
+            memcpy(status + j.lo, hb + L.status, m);
         }
     }
     return rc;
@@ -4082,14 +4560,6 @@ int mk_compute_device(mk_net *h, int device, const mk_input *in, size_t n, int32
     if (device < 0 || device >= ndev || device >= mk::kMaxDevices) return MK_EINVAL;
     std::lock_guard<std::mutex> lk(h->mu);
     return mk::launch_locked(h, device, in, n, d_out, d_status, d_steps, d_stats, opts, (hipStream_t)stream);
-}
-
-extern "C++" {
-namespace mk {
-namespace {
-uint64_t net_hash(const Network &N);
-}
-} // namespace mk
 }
 
 int mk_session_create(mk_net *h, int device, size_t n, const mk_opts *opts, mk_session **out)
@@ -4120,18 +4590,32 @@ int mk_session_create(mk_net *h, int device, size_t n, const mk_opts *opts, mk_s
     mk::DeviceGuard g(device);
     // one allocation, 256-byte aligned arrays, [field][session]
     const size_t N = n ? n : 1, P = (size_t)s->nprog, S = (size_t)s->nstack;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t sz[] = {al(P * N * 8), al(P * N * 8), al(P * N * 4), al(P * N * 4), al(P * 4 * N * 4), al(N * 8),
-                         al(N * 4),     al(N * 4),     al(N * 4),     al(N * 4),     al(S * N * 4),     al(S * cap * N * 4),
-                         al(P * N * 4), al(P * N * 4), al(N * 4),     al(N * 4)};
-    size_t total = 0;
-    for (size_t b : sz) total += b;
+    mk::SessParams &p = s->p;
+    // first over nothing, for the size, then over the allocation
+    auto carve = [&](void *base) {
+        mk::Carver k(base);
+        p.acc = k.take<int64_t>(P * N);
+        p.bak = k.take<int64_t>(P * N);
+        p.ip = k.take<int32_t>(P * N);
+        p.pendv = k.take<int32_t>(P * N);
+        p.port = k.take<int32_t>(P * 4 * N);
+        p.pfull = k.take<uint64_t>(N);
+        p.bits = k.take<uint32_t>(N);
+        p.io = k.take<uint32_t>(N);
+        p.in_val = k.take<int32_t>(N);
+        p.out_val = k.take<int32_t>(N);
+        p.sdepth = k.take<int32_t>(S * N);
+        p.stk = k.take<int32_t>(S * cap * N);
+        p.xst = k.take<uint32_t>(P * N);
+        p.xval = k.take<int32_t>(P * N);
+        p.pin = k.take<int32_t>(N);
+        p.csteps = k.take<uint32_t>(N);
+        return k.at;
+    };
+    const size_t total = carve(nullptr);
     if (hipMalloc(&s->d_state, total) != hipSuccess) return MK_ENOMEM;
     s->state_bytes = total;
-    char *b = (char *)s->d_state;
-    size_t off = 0;
-    auto take = [&](size_t i) { char *q = b + off; off += sz[i]; return q; };
-    mk::SessParams &p = s->p;
+    carve(s->d_state);
     for (int i = 0; i < s->nprog; i++) {
         p.base[i] = h->net.base[i];
         p.len[i] = h->net.len[i];
@@ -4141,22 +4625,6 @@ int mk_session_create(mk_net *h, int device, size_t n, const mk_opts *opts, mk_s
     p.n = n;
     p.budget = budget;
     p.stack_cap = cap;
-    p.acc = (int64_t *)take(0);
-    p.bak = (int64_t *)take(1);
-    p.ip = (int32_t *)take(2);
-    p.pendv = (int32_t *)take(3);
-    p.port = (int32_t *)take(4);
-    p.pfull = (uint64_t *)take(5);
-    p.bits = (uint32_t *)take(6);
-    p.io = (uint32_t *)take(7);
-    p.in_val = (int32_t *)take(8);
-    p.out_val = (int32_t *)take(9);
-    p.sdepth = (int32_t *)take(10);
-    p.stk = (int32_t *)take(11);
-    p.xst = (uint32_t *)take(12);
-    p.xval = (int32_t *)take(13);
-    p.pin = (int32_t *)take(14);
-    p.csteps = (uint32_t *)take(15);
     p.mixed = h->net.uses_remote ? 1u : 0u;
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return MK_EDEVICE;
     if (hipMemsetAsync(s->d_state, 0, total, s->stream) != hipSuccess) return MK_EDEVICE; // post-/reset state
@@ -4168,31 +4636,6 @@ int mk_session_create(mk_net *h, int device, size_t n, const mk_opts *opts, mk_s
     *out = s.release();
     return MK_OK;
 }
-
-namespace mk {
-// Orders work about to be queued on `to` after the session's last launch on
-// a caller stream: a device-side wait on the event recorded after that
-// launch, skipped when `to` is that same stream (stream order already holds;
-// the two-way event hand-off per call had cost ~20 us of stream latency per
-// launch, profiles/r06s_sessions_stream_order.txt).
-int session_wait_last(mk_session *s, hipStream_t to)
-{
-    if (!s->last || s->last == to) return MK_OK;
-    if (hipStreamWaitEvent(to, s->order, 0) != hipSuccess) return MK_EDEVICE;
-    if (to == s->stream) s->last = nullptr; // s->stream now follows every launch so far
-    return MK_OK;
-}
-
-// After a launch on `st` (a caller's or the session's own stream): work queued
-// later on any other stream waits on this.
-int session_mark(mk_session *s, hipStream_t st)
-{
-    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
-    if (hipEventRecord(s->order, st) != hipSuccess) return MK_EDEVICE;
-    s->last = st;
-    return MK_OK;
-}
-} // namespace mk
 
 int mk_session_reset(mk_session *s)
 {
@@ -4214,24 +4657,11 @@ int mk_session_compute_seq_device(mk_session *s, const int64_t *d_in, size_t nca
     if (!s || (s->n && ncalls && (!d_in || !d_out || !d_status))) return MK_EINVAL;
     if (ncalls > 0xffffffffull) return MK_EINVAL;
     std::lock_guard<std::mutex> lk(s->mu);
-    mk::DeviceGuard g(s->device);
-    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-    // the session state is ordered across streams device-side, with no host
-    // synchronisation: this launch after the previous one (a wait only when
-    // that ran on another stream), and the session's own stream's later work
-    // (reset, host calls) after this one
-    if (int rc = mk::session_wait_last(s, st)) return rc;
-    bool queued = false;
-    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
-    int rc = mk::session_launch(s, d_in, d_out, d_status, d_steps, st, (uint32_t)ncalls, false, &queued, s->order);
-    if (rc) {
-        // the native kernel may be running on `st` although the launch
-        // failed after it: reset and teardown must still wait for it
-        if (queued) (void)mk::session_mark(s, st);
-        return rc;
-    }
-    s->last = st; // the launch's last kernel recorded s->order (session_mark's event) on completion
-    return MK_OK;
+    mk::SessCall k = mk::SessCall::io(d_in, d_out, d_status, d_steps);
+    k.ncalls = (uint32_t)ncalls;
+    return mk::session_on_stream(s, stream, [&](hipStream_t st, bool *queued, hipEvent_t done) {
+        return mk::session_launch(s, k, st, queued, done);
+    });
 }
 
 int mk_session_compute_device(mk_session *s, const int64_t *d_in, int32_t *d_out, uint8_t *d_status,
@@ -4240,101 +4670,26 @@ int mk_session_compute_device(mk_session *s, const int64_t *d_in, int32_t *d_out
     return mk_session_compute_seq_device(s, d_in, 1, d_out, d_status, d_steps, stream);
 }
 
-extern "C++" {
-namespace mk {
-namespace {
-int session_host_calls(mk_session *s, const int64_t *in, size_t ncalls, int32_t *out, uint8_t *status,
-                       uint32_t *steps, bool resume);
-}
-} // namespace mk
-}
-
 int mk_session_compute_seq(mk_session *s, const int64_t *in, size_t ncalls, int32_t *out, uint8_t *status,
                            uint32_t *steps)
 {
     if (!s || (s->n && ncalls && (!in || !out || !status))) return MK_EINVAL;
-    return mk::session_host_calls(s, in, ncalls, out, status, steps, false);
+    if (s->n == 0 || ncalls == 0) return MK_OK;
+    if (ncalls > 0xffffffffull) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::HostIO io = mk::HostIO::of(s->n * ncalls, in, out, status, steps);
+    io.m = s->n;
+    return mk::session_host_burst(s, io, (uint32_t)ncalls);
 }
 
 int mk_session_step(mk_session *s, const int64_t *in, int32_t *out, uint8_t *status, uint32_t *steps)
 {
     if (!s || (s->n && (!out || !status))) return MK_EINVAL;
-    if (!in) { // resume: the kernel ignores the inputs
-        std::vector<int64_t> z(s->n ? s->n : 1, 0);
-        return mk::session_host_calls(s, z.data(), 1, out, status, steps, true);
-    }
-    return mk::session_host_calls(s, in, 1, out, status, steps, false);
-}
-
-extern "C++" {
-namespace mk {
-namespace {
-int session_host_calls(mk_session *s, const int64_t *in, size_t ncalls, int32_t *out, uint8_t *status,
-                       uint32_t *steps, bool resume)
-{
-    if (s->n == 0 || ncalls == 0) return MK_OK;
-    if (ncalls > 0xffffffffull) return MK_EINVAL;
+    if (s->n == 0) return MK_OK;
     std::lock_guard<std::mutex> lk(s->mu);
-    mk::DeviceGuard g(s->device);
-    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
-    const size_t m = s->n * ncalls;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t a8 = al(m * 8), a4 = al(m * 4), need = a8 + a4 + a4 + al(m);
-    // device buffers plus a pinned host mirror (small bursts are latency-bound:
-    // pinned copies avoid the runtime's pageable staging and its extra sync)
-    if (need > s->stage_bytes) {
-        (void)hipFree(s->d_stage);
-        (void)hipHostFree(s->h_stage);
-        s->d_stage = s->h_stage = nullptr;
-        s->stage_bytes = 0;
-        if (hipMalloc(&s->d_stage, need) != hipSuccess) return MK_ENOMEM;
-        if (hipHostMalloc(&s->h_stage, need, hipHostMallocDefault) != hipSuccess) return MK_ENOMEM;
-        s->stage_bytes = need;
-    }
-    char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
-    int64_t *din = (int64_t *)b;
-    int32_t *dout = (int32_t *)(b + a8);
-    uint32_t *dsteps = (uint32_t *)(b + a8 + a4);
-    uint8_t *dst = (uint8_t *)(b + a8 + a4 + a4);
-    memcpy(hb, in, m * 8);
-    if (hipMemcpyAsync(din, hb, m * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess) return MK_EDEVICE;
-    int rc = mk::session_launch(s, din, dout, dst, steps ? dsteps : nullptr, s->stream, (uint32_t)ncalls, resume);
-    if (rc) return rc;
-    if (hipMemcpyAsync(hb + a8, dout, m * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-        hipMemcpyAsync(hb + a8 + a4 + a4, dst, m, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    if (steps && hipMemcpyAsync(hb + a8 + a4, dsteps, m * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
-    memcpy(out, hb + a8, m * 4);
-    memcpy(status, hb + a8 + a4 + a4, m);
-    if (steps) memcpy(steps, hb + a8 + a4, m * 4);
-    // a session that had a call open when this launch began did nothing
-    // (MK_ST_CALL_OPEN): resume or cancel that call first
-    if (!resume)
-        for (size_t i = 0; i < s->n; i++)
-            if (status[i] == MK_ST_CALL_OPEN) return MK_EBUSY;
-    return MK_OK;
-}
-
-// One element of session state (device), read or written synchronously on
-// the session's stream (ordered after its launches).  Caller holds s->mu.
-template <class T>
-int sget(mk_session *s, const T *dev, T &v)
-{
-    if (int rc = session_wait_last(s, s->stream)) return rc;
-    if (hipMemcpyAsync(&v, dev, sizeof(T), hipMemcpyDeviceToHost, s->stream) != hipSuccess) return MK_EDEVICE;
-    return hipStreamSynchronize(s->stream) == hipSuccess ? MK_OK : MK_EDEVICE;
-}
-template <class T>
-int sput(mk_session *s, T *dev, const T &v)
-{
-    if (int rc = session_wait_last(s, s->stream)) return rc;
-    if (hipMemcpyAsync(dev, &v, sizeof(T), hipMemcpyHostToDevice, s->stream) != hipSuccess) return MK_EDEVICE;
-    return hipStreamSynchronize(s->stream) == hipSuccess ? MK_OK : MK_EDEVICE;
-}
-} // namespace
-} // namespace mk
+    mk::HostIO io = mk::HostIO::of(s->n, in, out, status, steps); // a null in: resume
+    io.m = s->n;
+    return mk::session_host_burst(s, io, 1);
 }
 
 int mk_session_compute(mk_session *s, const int64_t *in, int32_t *out, uint8_t *status, uint32_t *steps)
@@ -4492,121 +4847,31 @@ int mk_session_cancel(mk_session *s)
 }
 
 // ---- indexed forms: a launch on the m listed sessions only ------------------
-extern "C++" {
-namespace mk {
-namespace {
-// The host forms' check of an index list: at most n entries, strictly
-// increasing (so no two threads of a launch share a session), every one < n.
-bool sel_valid(const mk_session *s, const uint32_t *sel, size_t m)
-{
-    if (m > s->n || (m && !sel)) return false;
-    for (size_t t = 0; t < m; t++)
-        if (sel[t] >= s->n || (t && sel[t] <= sel[t - 1])) return false;
-    return true;
-}
-
-// The host-API staging (d_stage and its pinned mirror) with room for `need`
-// bytes.  Caller holds s->mu.
-int session_stage(mk_session *s, size_t need)
-{
-    if (need <= s->stage_bytes) return MK_OK;
-    (void)hipFree(s->d_stage);
-    (void)hipHostFree(s->h_stage);
-    s->d_stage = s->h_stage = nullptr;
-    s->stage_bytes = 0;
-    if (hipMalloc(&s->d_stage, need) != hipSuccess) return MK_ENOMEM;
-    if (hipHostMalloc(&s->h_stage, need, hipHostMallocDefault) != hipSuccess) return MK_ENOMEM;
-    s->stage_bytes = need;
-    return MK_OK;
-}
-
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// session_host_calls for an index list: the staging holds in, out, steps,
-// status ([ncalls][m] each) and then sel.
-int session_host_calls_sel(mk_session *s, const uint32_t *sel, size_t m, const int64_t *in, size_t ncalls,
-                           int32_t *out, uint8_t *status, uint32_t *steps, bool resume)
-{
-    if (ncalls > 0xffffffffull) return MK_EINVAL;
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (!sel_valid(s, sel, m)) return MK_EINVAL;
-    if (m == 0 || ncalls == 0) return MK_OK;
-    mk::DeviceGuard g(s->device);
-    if (int rc = session_wait_last(s, s->stream)) return rc;
-    const size_t c = m * ncalls;
-    const size_t a8 = al256(c * 8), a4 = al256(c * 4), a1 = al256(c), o_sel = a8 + a4 + a4 + a1;
-    if (int rc = session_stage(s, o_sel + al256(m * 4))) return rc;
-    char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
-    int64_t *din = (int64_t *)b;
-    int32_t *dout = (int32_t *)(b + a8);
-    uint32_t *dsteps = (uint32_t *)(b + a8 + a4);
-    uint8_t *dst = (uint8_t *)(b + a8 + a4 + a4);
-    uint32_t *dsel = (uint32_t *)(b + o_sel);
-    if (in) memcpy(hb, in, c * 8);
-    else memset(hb, 0, c * 8); // resume: the kernel ignores the inputs
-    memcpy(hb + o_sel, sel, m * 4);
-    if (hipMemcpyAsync(din, hb, c * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipMemcpyAsync(dsel, hb + o_sel, m * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    int rc = session_launch(s, din, dout, dst, steps ? dsteps : nullptr, s->stream, (uint32_t)ncalls, resume, nullptr,
-                            nullptr, dsel, m);
-    if (rc) return rc;
-    if (hipMemcpyAsync(hb + a8, dout, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-        hipMemcpyAsync(hb + a8 + a4 + a4, dst, c, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    if (steps && hipMemcpyAsync(hb + a8 + a4, dsteps, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
-    memcpy(out, hb + a8, c * 4);
-    memcpy(status, hb + a8 + a4 + a4, c);
-    if (steps) memcpy(steps, hb + a8 + a4, c * 4);
-    // a listed session that had a call open when this launch began did nothing
-    if (!resume)
-        for (size_t t = 0; t < m; t++)
-            if (status[t] == MK_ST_CALL_OPEN) return MK_EBUSY;
-    return MK_OK;
-}
-
-// The list on the device, in the staging (at its start), for the small
-// indexed kernels; *d_sel is null for a null list.  Caller holds s->mu and
-// has ordered s->stream after the set's last launch.
-int session_stage_sel(mk_session *s, const uint32_t *sel, size_t m, size_t extra, uint32_t **d_sel)
-{
-    const size_t a = sel ? al256(m * 4) : 0;
-    if (int rc = session_stage(s, a + extra)) return rc;
-    *d_sel = nullptr;
-    if (!sel) return MK_OK;
-    memcpy(s->h_stage, sel, m * 4);
-    if (hipMemcpyAsync(s->d_stage, s->h_stage, m * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    *d_sel = (uint32_t *)s->d_stage;
-    return MK_OK;
-}
-
-// Grid of the small indexed kernels: one thread per listed session.
-bool sel_grid(size_t m, unsigned *blocks)
-{
-    const uint64_t b = ((uint64_t)m + kBlock - 1) / kBlock;
-    if (b * kBlock > 0xffffffffull) return false;
-    *blocks = (unsigned)b;
-    return true;
-}
-} // namespace
-} // namespace mk
-}
-
 int mk_session_compute_indexed(mk_session *s, const uint32_t *sel, size_t m, const int64_t *in, size_t ncalls,
                                int32_t *out, uint8_t *status, uint32_t *steps)
 {
     if (!s || (m && ncalls && (!in || !out || !status))) return MK_EINVAL;
-    return mk::session_host_calls_sel(s, sel, m, in, ncalls, out, status, steps, false);
+    if (ncalls > 0xffffffffull) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!mk::sel_valid(s, sel, m)) return MK_EINVAL;
+    if (m == 0 || ncalls == 0) return MK_OK;
+    mk::HostIO io = mk::HostIO::of(m * ncalls, in, out, status, steps); // [ncalls][m] each
+    io.m = m;
+    io.sel = sel;
+    return mk::session_host_burst(s, io, (uint32_t)ncalls);
 }
 
 int mk_session_step_indexed(mk_session *s, const uint32_t *sel, size_t m, const int64_t *in, int32_t *out,
                             uint8_t *status, uint32_t *steps)
 {
     if (!s || (m && (!out || !status))) return MK_EINVAL;
-    return mk::session_host_calls_sel(s, sel, m, in, 1, out, status, steps, in == nullptr);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!mk::sel_valid(s, sel, m)) return MK_EINVAL;
+    if (m == 0) return MK_OK;
+    mk::HostIO io = mk::HostIO::of(m, in, out, status, steps); // a null in: resume
+    io.m = m;
+    io.sel = sel;
+    return mk::session_host_burst(s, io, 1);
 }
 
 int mk_session_compute_indexed_device(mk_session *s, const uint32_t *d_sel, size_t m, const int64_t *d_in,
@@ -4617,87 +4882,34 @@ int mk_session_compute_indexed_device(mk_session *s, const uint32_t *d_sel, size
     if (ncalls > 0xffffffffull || m > s->n) return MK_EINVAL;
     if (m == 0 || ncalls == 0) return MK_OK;
     std::lock_guard<std::mutex> lk(s->mu);
-    mk::DeviceGuard g(s->device);
-    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    mk::SessCall k = mk::SessCall::io(d_in, d_out, d_status, d_steps);
+    k.ncalls = (uint32_t)ncalls;
+    k.sel = d_sel;
+    k.m = m;
     // ordered against every other launch of the set, whatever it selected
-    // (mk_session_compute_seq_device)
-    if (int rc = mk::session_wait_last(s, st)) return rc;
-    bool queued = false;
-    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
-    int rc = mk::session_launch(s, d_in, d_out, d_status, d_steps, st, (uint32_t)ncalls, false, &queued, s->order,
-                                d_sel, m);
-    if (rc) {
-        if (queued) (void)mk::session_mark(s, st);
-        return rc;
-    }
-    s->last = st;
-    return MK_OK;
+    return mk::session_on_stream(s, stream, [&](hipStream_t st, bool *queued, hipEvent_t done) {
+        return mk::session_launch(s, k, st, queued, done);
+    });
 }
 
 // ---- ragged bursts: each listed session its own number of calls -------------
-extern "C++" {
-namespace mk {
-namespace {
-// session_host_calls_sel for a ragged burst: the staging holds in, out,
-// steps, status (off[m] words each), then off and, when given, sel.
-int session_host_calls_ragged(mk_session *s, const uint32_t *sel, size_t m, const uint32_t *off, const int64_t *in,
-                              int32_t *out, uint8_t *status, uint32_t *steps)
-{
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (sel ? !sel_valid(s, sel, m) : m != s->n) return MK_EINVAL; // a null list: every session, m == n
-    if (m == 0) return MK_OK;
-    if (off[0] != 0u) return MK_EINVAL;
-    for (size_t t = 0; t < m; t++)
-        if (off[t + 1] < off[t]) return MK_EINVAL;
-    const size_t c = off[m];
-    if (c == 0) return MK_OK;
-    if (!in || !out || !status) return MK_EINVAL;
-    mk::DeviceGuard g(s->device);
-    if (int rc = session_wait_last(s, s->stream)) return rc;
-    const size_t a8 = al256(c * 8), a4 = al256(c * 4), a1 = al256(c), o_off = a8 + a4 + a4 + a1;
-    const size_t o_sel = o_off + al256((m + 1) * 4);
-    if (int rc = session_stage(s, o_sel + (sel ? al256(m * 4) : 0))) return rc;
-    char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
-    int64_t *din = (int64_t *)b;
-    int32_t *dout = (int32_t *)(b + a8);
-    uint32_t *dsteps = (uint32_t *)(b + a8 + a4);
-    uint8_t *dst = (uint8_t *)(b + a8 + a4 + a4);
-    uint32_t *doff = (uint32_t *)(b + o_off);
-    uint32_t *dsel = sel ? (uint32_t *)(b + o_sel) : nullptr;
-    memcpy(hb, in, c * 8);
-    memcpy(hb + o_off, off, (m + 1) * 4);
-    if (sel) memcpy(hb + o_sel, sel, m * 4);
-    if (hipMemcpyAsync(din, hb, c * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipMemcpyAsync(doff, hb + o_off, (m + 1) * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        (sel && hipMemcpyAsync(dsel, hb + o_sel, m * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess))
-        return MK_EDEVICE;
-    int rc = session_launch(s, din, dout, dst, steps ? dsteps : nullptr, s->stream, 1, false, nullptr, nullptr, dsel, m,
-                            doff, (uint32_t)c);
-    if (rc) return rc;
-    if (hipMemcpyAsync(hb + a8, dout, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-        hipMemcpyAsync(hb + a8 + a4 + a4, dst, c, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    if (steps && hipMemcpyAsync(hb + a8 + a4, dsteps, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
-    memcpy(out, hb + a8, c * 4);
-    memcpy(status, hb + a8 + a4 + a4, c);
-    if (steps) memcpy(steps, hb + a8 + a4, c * 4);
-    // a listed session with a call to make that had one open when this launch
-    // began did nothing: its first call says so
-    for (size_t t = 0; t < m; t++)
-        if (off[t + 1] > off[t] && status[off[t]] == MK_ST_CALL_OPEN) return MK_EBUSY;
-    return MK_OK;
-}
-} // namespace
-} // namespace mk
-}
-
 int mk_session_compute_ragged(mk_session *s, const uint32_t *sel, size_t m, const uint32_t *off, const int64_t *in,
                               int32_t *out, uint8_t *status, uint32_t *steps)
 {
     if (!s || (m && !off)) return MK_EINVAL;
-    return mk::session_host_calls_ragged(s, sel, m, off, in, out, status, steps);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (sel ? !mk::sel_valid(s, sel, m) : m != s->n) return MK_EINVAL; // a null list: every session, m == n
+    if (m == 0) return MK_OK;
+    if (off[0] != 0u) return MK_EINVAL;
+    for (size_t t = 0; t < m; t++)
+        if (off[t + 1] < off[t]) return MK_EINVAL;
+    if (off[m] == 0) return MK_OK;
+    if (!in || !out || !status) return MK_EINVAL;
+    mk::HostIO io = mk::HostIO::of(off[m], in, out, status, steps); // compact, entry-major
+    io.m = m;
+    io.sel = sel;
+    io.off = off;
+    return mk::session_host_burst(s, io, 1);
 }
 
 int mk_session_compute_ragged_device(mk_session *s, const uint32_t *d_sel, size_t m, const uint32_t *d_off,
@@ -4708,21 +4920,14 @@ int mk_session_compute_ragged_device(mk_session *s, const uint32_t *d_sel, size_
     if (total > 0xffffffffull || m > s->n || (!d_sel && m && m != s->n)) return MK_EINVAL;
     if (m == 0 || total == 0) return MK_OK;
     std::lock_guard<std::mutex> lk(s->mu);
-    mk::DeviceGuard g(s->device);
-    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-    // ordered against every other launch of the set, whatever it selected
-    // (mk_session_compute_seq_device)
-    if (int rc = mk::session_wait_last(s, st)) return rc;
-    bool queued = false;
-    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
-    int rc = mk::session_launch(s, d_in, d_out, d_status, d_steps, st, 1, false, &queued, s->order, d_sel, m, d_off,
-                                (uint32_t)total);
-    if (rc) {
-        if (queued) (void)mk::session_mark(s, st);
-        return rc;
-    }
-    s->last = st;
-    return MK_OK;
+    mk::SessCall k = mk::SessCall::io(d_in, d_out, d_status, d_steps);
+    k.sel = d_sel;
+    k.m = m;
+    k.off = d_off;
+    k.total = (uint32_t)total;
+    return mk::session_on_stream(s, stream, [&](hipStream_t st, bool *queued, hipEvent_t done) {
+        return mk::session_launch(s, k, st, queued, done);
+    });
 }
 
 // ---- request queues: arrival order in, grouped on the GPU (req_group.h) -------
@@ -4753,107 +4958,6 @@ int mk_requests_group_device(int device, uint32_t n, const uint32_t *d_ids, size
     return mk::rg::rg_group(n, d_ids, (uint32_t)total, d_perm, d_sel, d_off, d_m, d_tmp, st);
 }
 
-extern "C++" {
-namespace mk {
-namespace {
-// The queue scratch of a set, for `total` requests.
-struct QueueBufs {
-    void *tmp;
-    uint32_t *perm, *sel, *off, *m;
-    int64_t *in;
-    int32_t *out;
-    uint32_t *steps;
-    uint8_t *status;
-    size_t bytes;
-};
-
-QueueBufs queue_layout(size_t n, size_t total, void *base)
-{
-    const size_t M = total < n ? total : n;
-    size_t at = 0;
-    auto take = [&](size_t b) {
-        const size_t o = at;
-        at += al256(b ? b : 1);
-        return (char *)base + o;
-    };
-    QueueBufs q{};
-    q.tmp = take(rg::rg_tmp_layout(total).bytes);
-    q.perm = (uint32_t *)take(total * 4);
-    q.sel = (uint32_t *)take(M * 4);
-    q.off = (uint32_t *)take((M + 1) * 4);
-    q.m = (uint32_t *)take(4);
-    q.in = (int64_t *)take(total * 8);
-    q.out = (int32_t *)take(total * 4);
-    q.steps = (uint32_t *)take(total * 4);
-    q.status = (uint8_t *)take(total);
-    q.bytes = at;
-    return q;
-}
-
-// Room for `total` requests.  Growing waits for the set's last launch -- it
-// may be reading the old scratch -- then frees and reallocates; a failed
-// allocation leaves the set without a scratch and usable.  Caller holds s->mu.
-int queue_reserve(mk_session *s, size_t total)
-{
-    if (total <= s->queue_cap) return MK_OK;
-    if (s->last && s->order && hipEventSynchronize(s->order) != hipSuccess) return MK_EDEVICE;
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
-    (void)hipFree(s->d_queue);
-    s->d_queue = nullptr;
-    s->queue_cap = 0;
-    const size_t cap = std::min<size_t>(std::max<size_t>(total + total / 2, 4096), 0xffffffffull);
-    if (hipMalloc(&s->d_queue, queue_layout(s->n, cap, nullptr).bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        s->d_queue = nullptr;
-        return MK_ENOMEM;
-    }
-    s->queue_cap = cap;
-    return MK_OK;
-}
-
-// The queue on `st`: group, gather, the ragged launch on the sorted arrays,
-// scatter.  Caller holds s->mu, has the device current and has ordered `st`
-// after the set's last launch; total in [1, 2^32), 1 <= s->n < 2^32.  d_busy:
-// rq_scatter's flag, or null.  A failure before the session kernel leaves the
-// set as it was: the grouping touches no session state.
-int queue_launch(mk_session *s, const uint32_t *d_ids, const int64_t *d_in, size_t total, int32_t *d_out,
-                 uint8_t *d_status, uint32_t *d_steps, uint32_t *d_busy, hipStream_t st)
-{
-    if (s->broken) return MK_EDEVICE;
-    if (int rc = queue_reserve(s, total)) return rc;
-    const QueueBufs q = queue_layout(s->n, s->queue_cap, s->d_queue);
-    const uint32_t n = (uint32_t)s->n, tot = (uint32_t)total;
-    const uint64_t M = total < s->n ? total : s->n;
-    const unsigned blocks = (unsigned)((total + rg::kRgBlock - 1) / rg::kRgBlock);
-    // whatever gets queued reads and writes the scratch: a later launch that grows it must wait
-    bool queued = true;
-    int rc = rg::rg_group(n, d_ids, tot, q.perm, q.sel, q.off, q.m, q.tmp, st);
-    if (rc == MK_OK) {
-        hipLaunchKernelGGL(rg::rq_gather, dim3(blocks), dim3(rg::kRgBlock), 0, st, d_in, (const uint32_t *)q.perm, tot,
-                           q.in);
-        if (hipGetLastError() != hipSuccess) rc = MK_EDEVICE;
-    }
-    if (rc == MK_OK)
-        rc = session_launch(s, q.in, q.out, q.status, d_steps ? q.steps : nullptr, st, 1, false, &queued, nullptr,
-                            q.sel, M, q.off, tot);
-    if (rc == MK_OK) {
-        // off[M] is the number of requests that name a session (req_group.h rg_tail)
-        hipLaunchKernelGGL(rg::rq_scatter, dim3(blocks), dim3(rg::kRgBlock), 0, st, (const uint32_t *)q.perm, d_ids, tot,
-                           (const uint32_t *)(q.off + M), (const int32_t *)q.out, (const uint8_t *)q.status,
-                           (const uint32_t *)q.steps, d_out, d_status, d_steps, d_busy);
-        if (hipGetLastError() != hipSuccess) rc = MK_EDEVICE;
-    }
-    // the scatter is the launch's last kernel: later work on another stream waits for it
-    if (queued) {
-        const int mr = session_mark(s, st);
-        if (rc == MK_OK) rc = mr;
-    }
-    return rc;
-}
-} // namespace
-} // namespace mk
-}
-
 int mk_session_compute_queue_device(mk_session *s, const uint32_t *d_ids, const int64_t *d_in, size_t total,
                                     int32_t *d_out, uint8_t *d_status, uint32_t *d_steps, void *stream)
 {
@@ -4863,8 +4967,8 @@ int mk_session_compute_queue_device(mk_session *s, const uint32_t *d_ids, const 
     if (s->n > 0xffffffffull) return MK_ELIMIT;
     std::lock_guard<std::mutex> lk(s->mu);
     mk::DeviceGuard g(s->device);
-    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-    if (int rc = mk::session_wait_last(s, st)) return rc;
+    hipStream_t st;
+    if (int rc = mk::session_enter(s, stream, &st)) return rc;
     if (s->n == 0) { // no id names a session
         if (s->broken) return MK_EDEVICE;
         if (hipMemsetAsync(d_out, 0, total * 4, st) != hipSuccess ||
@@ -4888,38 +4992,15 @@ int mk_session_compute_queue(mk_session *s, const uint32_t *ids, const int64_t *
     if (s->n > 0xffffffffull) return MK_ELIMIT;
     mk::DeviceGuard g(s->device);
     if (int rc = mk::session_wait_last(s, s->stream)) return rc;
-    // the staging holds in, out, steps, status, ids and the busy flag
-    const size_t c = total;
-    const size_t a8 = mk::al256(c * 8), a4 = mk::al256(c * 4), a1 = mk::al256(c);
-    const size_t o_ids = a8 + a4 + a4 + a1, o_busy = o_ids + a4;
-    if (int rc = mk::session_stage(s, o_busy + 256)) return rc;
-    char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
-    int64_t *din = (int64_t *)b;
-    int32_t *dout = (int32_t *)(b + a8);
-    uint32_t *dsteps = (uint32_t *)(b + a8 + a4);
-    uint8_t *dst = (uint8_t *)(b + a8 + a4 + a4);
-    uint32_t *dids = (uint32_t *)(b + o_ids), *dbusy = (uint32_t *)(b + o_busy);
-    memcpy(hb, in, c * 8);
-    memcpy(hb + o_ids, ids, c * 4);
-    if (hipMemcpyAsync(din, hb, c * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipMemcpyAsync(dids, hb + o_ids, c * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipMemsetAsync(dbusy, 0, 4, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    if (int rc = mk::queue_launch(s, dids, din, total, dout, dst, steps ? dsteps : nullptr, dbusy, s->stream)) return rc;
-    if (hipMemcpyAsync(hb + a8, dout, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-        hipMemcpyAsync(hb + a8 + a4 + a4, dst, c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-        hipMemcpyAsync(hb + o_busy, dbusy, 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    if (steps && hipMemcpyAsync(hb + a8 + a4, dsteps, c * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
-        return MK_EDEVICE;
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
-    memcpy(out, hb + a8, c * 4);
-    memcpy(status, hb + a8 + a4 + a4, c);
-    if (steps) memcpy(steps, hb + a8 + a4, c * 4);
+    uint32_t busy = 0;
+    mk::HostIO io = mk::HostIO::of(total, in, out, status, steps);
+    io.ids = ids;
+    io.flag = &busy;
+    int rc = mk::session_round_trip(s, io, [&](const mk::StageDev &d) {
+        return mk::queue_launch(s, d.ids, d.in, total, d.out, d.status, d.steps, d.flag, s->stream);
+    });
     // the first request of a session that had a call open when this launch began did nothing
-    uint32_t busy;
-    memcpy(&busy, hb + o_busy, 4);
-    return busy ? MK_EBUSY : MK_OK;
+    return rc ? rc : busy ? MK_EBUSY : MK_OK;
 }
 
 int mk_session_cancel_indexed(mk_session *s, const uint32_t *sel, size_t m)
@@ -4933,7 +5014,7 @@ int mk_session_cancel_indexed(mk_session *s, const uint32_t *sel, size_t m)
     mk::DeviceGuard g(s->device);
     if (int rc = mk::session_wait_last(s, s->stream)) return rc;
     uint32_t *d_sel;
-    if (int rc = mk::session_stage_sel(s, sel, m, 0, &d_sel)) return rc;
+    if (int rc = mk::session_stage_sel(s, sel, m, nullptr, &d_sel)) return rc;
     uint32_t *io = s->p.io;
     uint64_t n = s->n, mm = m;
     void *args[] = {(void *)&io, (void *)&n, (void *)&d_sel, (void *)&mm};
@@ -4954,7 +5035,7 @@ int mk_session_reset_indexed(mk_session *s, const uint32_t *sel, size_t m)
     mk::DeviceGuard g(s->device);
     if (int rc = mk::session_wait_last(s, s->stream)) return rc;
     uint32_t *d_sel;
-    if (int rc = mk::session_stage_sel(s, sel, m, 0, &d_sel)) return rc;
+    if (int rc = mk::session_stage_sel(s, sel, m, nullptr, &d_sel)) return rc;
     mk::SessParams p = s->p;
     mk::SessResetSel q{};
     if (s->native) q = mk::SessResetSel{s->nsb, s->hand_sb, s->hand_steps, s->hand_call, s->sflags, s->regs, s->slots,
@@ -4987,8 +5068,8 @@ int mk_session_call_open(mk_session *s, const uint32_t *sel, size_t m, uint8_t *
     mk::DeviceGuard g(s->device);
     if (int rc = mk::session_wait_last(s, s->stream)) return rc;
     uint32_t *d_sel;
-    if (int rc = mk::session_stage_sel(s, sel, m, mk::al256(m), &d_sel)) return rc;
-    const size_t o_open = sel ? mk::al256(m * 4) : 0;
+    size_t o_open = m; // m bytes behind the list
+    if (int rc = mk::session_stage_sel(s, sel, m, &o_open, &d_sel)) return rc;
     uint8_t *d_open = (uint8_t *)s->d_stage + o_open;
     const uint32_t *io = s->p.io;
     uint64_t n = s->n, mm = m;
@@ -5004,131 +5085,6 @@ int mk_session_call_open(mk_session *s, const uint32_t *sel, size_t m, uint8_t *
 }
 
 // ---- snapshots: session records out of a set and back (sess_record.h) --------
-extern "C++" {
-namespace mk {
-namespace {
-// What identifies a network to a record: FNV-1a over the node names, their
-// kinds and the lowered bytecode.
-uint64_t net_hash(const Network &N)
-{
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](const void *p, size_t k) {
-        for (size_t i = 0; i < k; i++) h = (h ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
-    };
-    auto str = [&](const std::string &x, int kind) {
-        mix(x.c_str(), x.size() + 1);
-        mix(&kind, sizeof kind);
-    };
-    for (const std::string &x : N.prog_names) str(x, NK_PROGRAM);
-    for (const std::string &x : N.stack_names) str(x, NK_STACK);
-    for (size_t i = 0; i < N.remote_names.size(); i++) str(N.remote_names[i], N.remote_kinds[i]);
-    for (size_t k = 0; k < N.base.size(); k++) {
-        mix(&N.base[k], 4);
-        mix(&N.len[k], 4);
-    }
-    for (const Insn &I : N.code) {
-        const int64_t w[6] = {I.op, I.src, I.dst, I.arg, I.imm, 0};
-        mix(w, sizeof w);
-    }
-    return h;
-}
-
-SessRecShape session_shape(const mk_session *s) { return SessRecShape{s->nprog, s->nstack, s->cap, s->nregs, s->nslots}; }
-
-void session_layout(const mk_session *s, mk_session_layout *out)
-{
-    const SessRecShape L = session_shape(s);
-    *out = mk_session_layout{};
-    out->magic = kSessRecMagic;
-    out->version = kSessRecVersion;
-    out->net_hash = s->net_hash;
-    out->native_hash = s->native ? s->native_hash : 0;
-    out->nprog = (uint32_t)s->nprog;
-    out->nstack = (uint32_t)s->nstack;
-    out->stack_cap = s->cap;
-    out->native_rows = s->native ? L.native_rows() : 0u;
-    out->rows = L.canon_rows() + out->native_rows;
-}
-
-// A block's layout against the set's: the canonical part must be this
-// network's at this stack_cap, the block's row count its own sections'.
-bool layout_fits(const mk_session *s, const mk_session_layout *from)
-{
-    mk_session_layout own;
-    session_layout(s, &own);
-    return from->magic == own.magic && from->version == own.version && from->net_hash == own.net_hash &&
-           from->nprog == own.nprog && from->nstack == own.nstack && from->stack_cap == own.stack_cap &&
-           from->rows == own.rows - own.native_rows + from->native_rows && from->rows >= from->native_rows;
-}
-
-// the block's native section is this set's own
-bool layout_native(const mk_session *s, const mk_session_layout *from)
-{
-    return s->native && from->native_hash != 0 && from->native_hash == s->native_hash &&
-           from->native_rows == session_shape(s).native_rows();
-}
-
-SessSnapK session_snapk(const mk_session *s, bool nat_ok)
-{
-    SessSnapK q{};
-    if (s->native)
-        q = SessSnapK{s->nsb, s->hand_sb, s->hand_steps, s->hand_call, s->sflags, s->regs, s->slots, s->nregs,
-                      s->nslots, s->hdr, s->rec, s->dyn_base, s->pre, s->nsbk, nat_ok ? 1u : 0u};
-    return q;
-}
-
-// Grid of the two kernels: one thread per entry, the tall row groups over y.
-dim3 snap_grid(const mk_session *s, unsigned blocks)
-{
-    const uint64_t tall = std::max<uint64_t>(
-        {(uint64_t)s->nstack * s->cap, s->native ? 2ull * s->nregs : 0ull, s->native ? (uint64_t)s->nslots : 0ull, 1ull});
-    return dim3(blocks, (unsigned)std::min<uint64_t>(tall, 64));
-}
-
-// Queues the export of m entries (sessions d_sel[t], or first + t) into the
-// device block d_rec on `st`; `done` as in session_launch.
-int snapshot_launch(mk_session *s, const uint32_t *d_sel, uint64_t first, uint64_t m, uint32_t *d_rec, hipStream_t st,
-                    hipEvent_t done)
-{
-    unsigned blocks;
-    if (!sel_grid(m, &blocks)) return MK_ELIMIT;
-    SessParams p = s->p;
-    SessSnapK q = session_snapk(s, false);
-    void *args[] = {(void *)&p, (void *)&q, (void *)&d_sel, (void *)&first, (void *)&m, (void *)&d_rec};
-    return hipExtLaunchKernel(reinterpret_cast<void *>(&tis_session_export_sel), snap_grid(s, blocks), dim3(kBlock), args,
-                              0, st, nullptr, done, 0) == hipSuccess
-               ? MK_OK
-               : MK_EDEVICE;
-}
-
-// may_hold: a record of the block may be restored from its canonical part.
-int restore_launch(mk_session *s, const uint32_t *d_sel, uint64_t first, uint64_t m, bool nat_ok, bool may_hold,
-                   const uint32_t *d_rec, uint64_t mcols, const uint32_t *d_col, hipStream_t st, hipEvent_t done)
-{
-    unsigned blocks;
-    if (!sel_grid(m, &blocks)) return MK_ELIMIT;
-    SessParams p = s->p;
-    SessSnapK q = session_snapk(s, nat_ok);
-    void *args[] = {(void *)&p,     (void *)&q,     (void *)&d_sel, (void *)&first,
-                    (void *)&m,     (void *)&d_rec, (void *)&mcols, (void *)&d_col};
-    if (hipExtLaunchKernel(reinterpret_cast<void *>(&tis_session_restore_sel), snap_grid(s, blocks), dim3(kBlock), args,
-                           0, st, nullptr, done, 0) != hipSuccess)
-        return MK_EDEVICE;
-    if (may_hold) s->interp_may_hold = true; // a canonical restore hands its session to the interpreter
-    return MK_OK;
-}
-
-// Entries of a host form's staging chunk: at most 64 MiB of rows.
-size_t snap_chunk(uint32_t rows, size_t m) { return std::min<size_t>(m, std::max<size_t>(1, ((size_t)64 << 20) / ((size_t)rows * 4))); }
-
-struct DevBlock {
-    void *p = nullptr;
-    ~DevBlock() { (void)hipFree(p); }
-};
-} // namespace
-} // namespace mk
-}
-
 int mk_session_layout_get(const mk_session *s, mk_session_layout *out)
 {
     if (!s || !out) return MK_EINVAL;
@@ -5153,7 +5109,7 @@ int mk_session_snapshot(mk_session *s, const uint32_t *sel, size_t m, uint32_t *
     mk::DevBlock blk;
     if (hipMalloc(&blk.p, (size_t)lay.rows * chunk * 4) != hipSuccess) return MK_ENOMEM;
     uint32_t *d_sel;
-    if (int rc = mk::session_stage_sel(s, sel, m, 0, &d_sel)) return rc;
+    if (int rc = mk::session_stage_sel(s, sel, m, nullptr, &d_sel)) return rc;
     for (size_t t0 = 0; t0 < m; t0 += chunk) {
         const size_t c = std::min(chunk, m - t0);
         if (int rc = mk::snapshot_launch(s, d_sel ? d_sel + t0 : nullptr, t0, c, (uint32_t *)blk.p, s->stream, nullptr))
@@ -5174,14 +5130,10 @@ int mk_session_snapshot_device(mk_session *s, const uint32_t *d_sel, size_t m, u
     if (s->p.mixed || m > s->n || (!d_sel && m != s->n)) return MK_EINVAL;
     if (s->broken) return MK_EDEVICE;
     if (m == 0) return MK_OK;
-    mk::DeviceGuard g(s->device);
-    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-    // ordered against every other launch of the set (mk_session_compute_seq_device)
-    if (int rc = mk::session_wait_last(s, st)) return rc;
-    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
-    if (int rc = mk::snapshot_launch(s, d_sel, 0, m, d_rec, st, s->order)) return rc;
-    s->last = st;
-    return MK_OK;
+    // ordered against every other launch of the set; a failed launch has queued nothing
+    return mk::session_on_stream(s, stream, [&](hipStream_t st, bool *, hipEvent_t done) {
+        return mk::snapshot_launch(s, d_sel, 0, m, d_rec, st, done);
+    });
 }
 
 int mk_session_restore(mk_session *s, const uint32_t *sel, size_t m, const mk_session_layout *from,
@@ -5221,7 +5173,7 @@ int mk_session_restore(mk_session *s, const uint32_t *sel, size_t m, const mk_se
         return MK_ENOMEM;
     }
     uint32_t *d_sel;
-    if (int rc = mk::session_stage_sel(s, sel, m, 0, &d_sel)) return rc;
+    if (int rc = mk::session_stage_sel(s, sel, m, nullptr, &d_sel)) return rc;
     for (size_t t0 = 0; t0 < m; t0 += chunk) {
         const size_t c = std::min(chunk, m - t0);
         // the chunk's records gathered into a dense [row][c] block: entry j takes its column j
@@ -5247,15 +5199,9 @@ int mk_session_restore_device(mk_session *s, const uint32_t *d_sel, size_t m, co
     if (m > s->n || (!d_sel && m != s->n) || (!d_col && m > mcols)) return MK_EINVAL;
     if (s->broken) return MK_EDEVICE;
     if (m == 0) return MK_OK;
-    mk::DeviceGuard g(s->device);
-    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-    if (int rc = mk::session_wait_last(s, st)) return rc;
-    if (!s->order && hipEventCreateWithFlags(&s->order, hipEventDisableTiming) != hipSuccess) return MK_EDEVICE;
-    if (int rc = mk::restore_launch(s, d_sel, 0, m, mk::layout_native(s, from), true, d_rec, mcols, d_col, st,
-                                    s->order))
-        return rc;
-    s->last = st;
-    return MK_OK;
+    return mk::session_on_stream(s, stream, [&](hipStream_t st, bool *, hipEvent_t done) {
+        return mk::restore_launch(s, d_sel, 0, m, mk::layout_native(s, from), true, d_rec, mcols, d_col, st, done);
+    });
 }
 
 int mk_session_plan(const mk_session *s, char *out, size_t out_len)

@@ -18,6 +18,7 @@
 #include "tis_sched.h"
 #include "sess_convert.h"
 #include "sess_record.h"
+#include "sess_stage.h"
 
 namespace {
 
@@ -621,6 +622,17 @@ int mkc_tokenize(const char *program, char *out, size_t out_len)
     if (s.size() + 1 > out_len) return -3;
     std::memcpy(out, s.c_str(), s.size() + 1);
     return ok ? 0 : -2;
+}
+
+// The staging layout of a session set's host forms (sess_stage.h), as
+// mk_exec.hip cuts d_stage and its mirror: c I/O words, an index list and
+// offsets for m entries; extras bit 0 sel, 1 off, 2 ids, 3 the flag.
+// out: the offsets of in, out, steps, status, off, sel, ids, flag, then bytes.
+void mkc_stage_layout(size_t c, size_t m, unsigned extras, size_t *out)
+{
+    const mk::StageLayout L = mk::stage_layout(c, m, extras & 1u, extras & 2u, extras & 4u, extras & 8u);
+    const size_t v[9] = {L.in, L.out, L.steps, L.status, L.off, L.sel, L.ids, L.flag, L.bytes};
+    std::memcpy(out, v, sizeof v);
 }
 
 } // extern "C"

@@ -43,6 +43,11 @@ def _close_live():
             pass
 
 
+def _ptr(a):
+    """A host array as the C ABI takes it; None is the null pointer."""
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
 class TisParseError(ValueError):
     """A program was rejected; ``str(e)`` is the reference's Go error text."""
 
@@ -213,11 +218,11 @@ class Network:
         o = make_opts(budget, stack_cap, stop_on_output, devices, interp, mode)
         rc = N.lib().mk_compute_batch(
             self._h,
-            v.ctypes.data_as(C.c_void_p),
+            _ptr(v),
             n,
-            out.ctypes.data_as(C.c_void_p),
-            st.ctypes.data_as(C.c_void_p),
-            sp.ctypes.data_as(C.c_void_p) if sp is not None else None,
+            _ptr(out),
+            _ptr(st),
+            _ptr(sp),
             C.byref(o),
         )
         N.check(rc, "mk_compute_batch")
@@ -281,7 +286,7 @@ class Network:
         cnt = C.c_uint32()
         st = C.c_uint8()
         o = make_opts(budget, stack_cap, stop_on_output)
-        N.check(N.lib().mk_trace_lane(self._h, device, int(value), C.byref(o), out.ctypes.data_as(C.c_void_p),
+        N.check(N.lib().mk_trace_lane(self._h, device, int(value), C.byref(o), _ptr(out),
                                       max_entries, C.byref(cnt), C.byref(st)), "mk_trace_lane")
         return out[: cnt.value], st.value
 
@@ -343,40 +348,30 @@ class SessionSet:
             sel = self._index(index)
             if v.size != sel.size:
                 raise ValueError(f"expected {sel.size} values, got {v.size}")
-            return self._step_indexed(sel, v, steps, busy_ok)
+            return self._call("mk_session_step_indexed", sel.size, steps, busy_ok, _ptr(sel), sel.size, _ptr(v))
         if v.size != self.n:
             raise ValueError(f"expected {self.n} values, got {v.size}")
-        return self._step(v.ctypes.data_as(C.c_void_p), steps, busy_ok, "mk_session_compute")
+        return self._call("mk_session_compute", self.n, steps, busy_ok, _ptr(v))
 
     def resume(self, *, steps=True, index=None) -> BatchResult:
         """One more budget slice of every instance's open call (instances
         without one report status 0) -- mk_session_step(in = NULL); with
         ``index``, of the listed instances' open calls only."""
         if index is not None:
-            return self._step_indexed(self._index(index), None, steps, False)
-        return self._step(None, steps, False, "mk_session_step")
+            sel = self._index(index)
+            return self._call("mk_session_step_indexed", sel.size, steps, False, _ptr(sel), sel.size, None)
+        return self._call("mk_session_step", self.n, steps, False, None)
 
-    def _step_indexed(self, sel, v, steps, busy_ok) -> BatchResult:
-        m = sel.size
-        out = np.zeros(m, np.int32)
-        st = np.zeros(m, np.uint8)
-        sp = np.zeros(m, np.uint32) if steps else None
-        rc = N.lib().mk_session_step_indexed(
-            self._h, sel.ctypes.data_as(C.c_void_p), m, v.ctypes.data_as(C.c_void_p) if v is not None else None,
-            out.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p),
-            sp.ctypes.data_as(C.c_void_p) if sp is not None else None)
+    def _call(self, name, shape, steps, busy_ok, *args) -> BatchResult:
+        """One host form of the C ABI, ``N.lib().<name>(set, *args, out, status,
+        steps)``, into fresh result arrays of ``shape``.  MkError names
+        ``name``; MK_EBUSY passes with ``busy_ok``."""
+        out = np.zeros(shape, np.int32)
+        st = np.zeros(shape, np.uint8)
+        sp = np.zeros(shape, np.uint32) if steps else None
+        rc = getattr(N.lib(), name)(self._h, *args, _ptr(out), _ptr(st), _ptr(sp))
         if not (busy_ok and rc == N.MK_EBUSY):
-            N.check(rc, "mk_session_step_indexed")
-        return BatchResult(out, st, sp)
-
-    def _step(self, vp, steps, busy_ok, what) -> BatchResult:
-        out = np.zeros(self.n, np.int32)
-        st = np.zeros(self.n, np.uint8)
-        sp = np.zeros(self.n, np.uint32) if steps else None
-        rc = N.lib().mk_session_step(self._h, vp, out.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p),
-                                     sp.ctypes.data_as(C.c_void_p) if sp is not None else None)
-        if not (busy_ok and rc == N.MK_EBUSY):
-            N.check(rc, what)
+            N.check(rc, name)
         return BatchResult(out, st, sp)
 
     def plan(self) -> str:
@@ -390,7 +385,7 @@ class SessionSet:
         ``index``, the listed instances' only."""
         if index is not None:
             sel = self._index(index)
-            N.check(N.lib().mk_session_cancel_indexed(self._h, sel.ctypes.data_as(C.c_void_p), sel.size),
+            N.check(N.lib().mk_session_cancel_indexed(self._h, _ptr(sel), sel.size),
                     "mk_session_cancel_indexed")
             return
         N.check(N.lib().mk_session_cancel(self._h), "mk_session_cancel")
@@ -401,8 +396,7 @@ class SessionSet:
         sel = self._index(index) if index is not None else None
         m = self.n if sel is None else sel.size
         op = np.zeros(m, np.uint8)
-        N.check(N.lib().mk_session_call_open(self._h, sel.ctypes.data_as(C.c_void_p) if sel is not None else None, m,
-                                             op.ctypes.data_as(C.c_void_p)), "mk_session_call_open")
+        N.check(N.lib().mk_session_call_open(self._h, _ptr(sel), m, _ptr(op)), "mk_session_call_open")
         return op
 
     def compute_seq(self, values, *, steps=True, busy_ok=False, index=None) -> BatchResult:
@@ -418,32 +412,13 @@ class SessionSet:
             sel = self._index(index)
             if v.ndim != 2 or v.shape[1] != sel.size:
                 raise ValueError(f"expected (ncalls, {sel.size}) values, got {shape}")
-            out = np.zeros(shape, np.int32)
-            st = np.zeros(shape, np.uint8)
-            sp = np.zeros(shape, np.uint32) if steps else None
-            if v.size:
-                rc = N.lib().mk_session_compute_indexed(
-                    self._h, sel.ctypes.data_as(C.c_void_p), sel.size, v.ctypes.data_as(C.c_void_p), shape[0],
-                    out.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p),
-                    sp.ctypes.data_as(C.c_void_p) if sp is not None else None)
-                if not (busy_ok and rc == N.MK_EBUSY):
-                    N.check(rc, "mk_session_compute_indexed")
-            return BatchResult(out, st, sp)
+            return self._call("mk_session_compute_indexed", shape, steps, busy_ok, _ptr(sel), sel.size, _ptr(v),
+                              shape[0])
         if v.ndim == 1 and self.n == 1:
             v = v.reshape(-1, 1)
         if v.ndim != 2 or v.shape[1] != self.n:
             raise ValueError(f"expected (ncalls, {self.n}) values, got {shape}")
-        m = v.shape[0]
-        out = np.zeros(v.shape, np.int32)
-        st = np.zeros(v.shape, np.uint8)
-        sp = np.zeros(v.shape, np.uint32) if steps else None
-        if m:
-            rc = N.lib().mk_session_compute_seq(self._h, v.ctypes.data_as(C.c_void_p), m,
-                                                out.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p),
-                                                sp.ctypes.data_as(C.c_void_p) if sp is not None else None)
-            if not (busy_ok and rc == N.MK_EBUSY):
-                N.check(rc, "mk_session_compute_seq")
-        return BatchResult(out.reshape(shape), st.reshape(shape), sp.reshape(shape) if sp is not None else None)
+        return self._call("mk_session_compute_seq", shape, steps, busy_ok, _ptr(v), v.shape[0])
 
     def compute_device(self, in_ptr, out_ptr, status_ptr, steps_ptr=None, *, stream=None, index_ptr=None, m=None):
         """One call on device arrays, asynchronous on ``stream``.  With
@@ -525,18 +500,7 @@ class SessionSet:
         m = self.n if sel is None else sel.size
         if off.size - 1 != m:
             raise ValueError(f"expected {m} entries, got {off.size - 1}")
-        total = int(off[-1])
-        out = np.zeros(total, np.int32)
-        st = np.zeros(total, np.uint8)
-        sp = np.zeros(total, np.uint32) if steps else None
-        if total:
-            rc = N.lib().mk_session_compute_ragged(
-                self._h, sel.ctypes.data_as(C.c_void_p) if sel is not None else None, m,
-                off.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
-                st.ctypes.data_as(C.c_void_p), sp.ctypes.data_as(C.c_void_p) if sp is not None else None)
-            if not (busy_ok and rc == N.MK_EBUSY):
-                N.check(rc, "mk_session_compute_ragged")
-        return BatchResult(out, st, sp)
+        return self._call("mk_session_compute_ragged", int(off[-1]), steps, busy_ok, _ptr(sel), m, _ptr(off), _ptr(v))
 
     def compute_ragged_device(self, in_ptr, off_ptr, total, out_ptr, status_ptr, steps_ptr=None, *, stream=None,
                               index_ptr=None, m=None):
@@ -596,18 +560,7 @@ class SessionSet:
         MkError(MK_EBUSY) unless ``busy_ok`` when the first request of an
         instance found a call open."""
         q, v = self._queue(ids, values)
-        total = q.size
-        out = np.zeros(total, np.int32)
-        st = np.zeros(total, np.uint8)
-        sp = np.zeros(total, np.uint32) if steps else None
-        if total:
-            rc = N.lib().mk_session_compute_queue(
-                self._h, q.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), total,
-                out.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p),
-                sp.ctypes.data_as(C.c_void_p) if sp is not None else None)
-            if not (busy_ok and rc == N.MK_EBUSY):
-                N.check(rc, "mk_session_compute_queue")
-        return BatchResult(out, st, sp)
+        return self._call("mk_session_compute_queue", q.size, steps, busy_ok, _ptr(q), _ptr(v), q.size)
 
     def compute_queue_device(self, ids_ptr, in_ptr, total, out_ptr, status_ptr, steps_ptr=None, *, stream=None):
         """A request queue on device arrays of ``total`` words each,
@@ -625,7 +578,7 @@ class SessionSet:
         state; with ``index``, the listed instances only."""
         if index is not None:
             sel = self._index(index)
-            N.check(N.lib().mk_session_reset_indexed(self._h, sel.ctypes.data_as(C.c_void_p), sel.size),
+            N.check(N.lib().mk_session_reset_indexed(self._h, _ptr(sel), sel.size),
                     "mk_session_reset_indexed")
             return
         N.check(N.lib().mk_session_reset(self._h), "mk_session_reset")
@@ -645,8 +598,7 @@ class SessionSet:
         m = self.n if sel is None else sel.size
         lay = self.layout()
         rec = np.zeros((lay.rows, m), np.uint32)
-        N.check(N.lib().mk_session_snapshot(self._h, sel.ctypes.data_as(C.c_void_p) if sel is not None else None, m,
-                                            rec.ctypes.data_as(C.c_void_p)), "mk_session_snapshot")
+        N.check(N.lib().mk_session_snapshot(self._h, _ptr(sel), m, _ptr(rec)), "mk_session_snapshot")
         return SessionSnapshot(lay, rec)
 
     def _layout_fits(self, lay):
@@ -689,9 +641,7 @@ class SessionSet:
             col = np.ascontiguousarray(a.astype(np.uint32))
         elif m > mcols:
             raise ValueError(f"take position {mcols}: the snapshot has {mcols} columns for {m} instances")
-        rc = N.lib().mk_session_restore(self._h, sel.ctypes.data_as(C.c_void_p) if sel is not None else None, m,
-                                        C.byref(snap.layout), rec.ctypes.data_as(C.c_void_p), mcols,
-                                        col.ctypes.data_as(C.c_void_p) if col is not None else None)
+        rc = N.lib().mk_session_restore(self._h, _ptr(sel), m, C.byref(snap.layout), _ptr(rec), mcols, _ptr(col))
         if rc == N.MK_EINVAL:
             raise ValueError("snapshot record out of range (held, an ip, a stack depth or the native superblock): "
                              "nothing restored")
