@@ -1,5 +1,5 @@
 // tis_jit.cpp -- code generator of tier 3 (see tis_jit.h).  Host C++ only:
-// it produces source text; mk_exec.hip compiles it with hiprtc and the check
+// it produces source text; mk_rtc.cpp compiles it with hiprtc and the check
 // library (sched_check.cpp) exposes the lane function to the CPU tests, which
 // compile it with g++ and compare it with the oracle.
 //

@@ -159,7 +159,7 @@ struct JitLimits {
     bool prof = false;
 
     // VGPRs per SIMD lane a module's waves share when a stack plan's module
-    // is checked against its waves per SIMD (mk_exec.hip module_holds):
+    // is checked against its waves per SIMD (mk_rtc.cpp module_holds):
     // gfx950's 512.  MK_JIT_VGPR_FILE lowers it so that tests reach the
     // rejection path (the next plan, last the default) on purpose.
     uint32_t vgpr_file = 512;

@@ -241,23 +241,32 @@ def session_module(nodes, *, stack_cap=None):
         lib().mkc_free(h)
 
 
-# ---- test tool: a standalone hiprtc compiler (tests/native/rtc_compile.cpp)
+# ---- test tool: the product's run-time compiler (csrc/mk_rtc.cpp) behind a
+# stand-alone driver (tests/native/rtc_compile.cpp)
 
 _TOOL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native")
 
 
-def rtc_tool():
-    """Path of the built test compiler (this ROCm's hiprtc in a process of its
-    own that never loads PyTorch); rebuilt when its source changes."""
+def rtc_tool(sanitize=False):
+    """Path of the built test compiler (mk_rtc.cpp and its driver, in a process
+    of its own that never loads PyTorch); rebuilt when a source changes.
+    sanitize=True: the AddressSanitizer + UndefinedBehaviorSanitizer build, a
+    second program."""
     import hashlib
     import subprocess
 
-    src = os.path.join(_TOOL_DIR, "rtc_compile.cpp")
-    out = os.path.join(_TOOL_DIR, "build", "rtc_compile")
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", src,
-           "-L/opt/rocm/lib", "-lhiprtc", "-Wl,-rpath,/opt/rocm/lib"]
-    with open(src, "rb") as f:
-        stamp = hashlib.sha256(f.read() + " ".join(cmd).encode()).hexdigest()
+    import __graft_entry__ as g
+
+    srcs = [os.path.join(_TOOL_DIR, "rtc_compile.cpp"), os.path.join(g.CSRC, "mk_rtc.cpp")]
+    out = os.path.join(_TOOL_DIR, "build", "rtc_compile_san" if sanitize else "rtc_compile")
+    cmd = (["g++", "-std=c++17", "-Wall"] + (g.SAN_FLAGS if sanitize else ["-O2"]) +
+           ["-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"] + srcs +
+           ["-L/opt/rocm/lib", "-lhiprtc", "-ldl", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"])
+    h = hashlib.sha256(" ".join(cmd).encode())
+    for dep in srcs + [os.path.join(g.CSRC, "mk_rtc.h")]:
+        with open(dep, "rb") as f:
+            h.update(b"\0" + f.read())
+    stamp = h.hexdigest()
     try:
         with open(out + ".stamp") as f:
             if f.read().strip() == stamp and os.path.exists(out):

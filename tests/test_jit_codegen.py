@@ -533,7 +533,7 @@ def test_knobs_are_snapshotted_per_network(monkeypatch):
 
 
 # The native tier's modules are code object v5 whichever hiprtc builds them
-# (mk_exec.hip kCodeObjectVersion, mk_rtc.cpp): ROCm 7.2's default v6 modules
+# (mk_rtc.cpp kCodeObjectVersion): ROCm 7.2's default v6 modules
 # corrupted the host heap inside PyTorch's bundled HIP runtime (r03c-r03k).
 # The module of a dynamic-stack network (the shape that showed it), dumped by
 # MK_JIT_DUMP, read with llvm-readelf: ELF ABI version 3 = code object v5.

@@ -1,10 +1,16 @@
-"""Which compiler builds the native tier's modules (mk_exec.hip rtc_choice).
+"""Which compiler builds the native tier's modules (mk_rtc.cpp rtc_choice).
 
 In a process that imported PyTorch first, the linked hiprtc symbols resolve
 to PyTorch's bundled copy; the library then compiles with this ROCm's hiprtc
 opened in a link-map namespace of its own (dlmopen), on one compile thread.
 No GPU is needed: mk_net_plan compiles the module.  Each case runs in a
-subprocess so that the process's import order is the one under test."""
+subprocess so that the process's import order is the one under test.
+
+The run-time compiler is a host unit of its own (csrc/mk_rtc.cpp); the
+stand-alone driver (tests/native/rtc_compile.cpp, schedcheck.rtc_tool) links
+it without Python, PyTorch or the HIP runtime, plain and under AddressSanitizer
++ UndefinedBehaviorSanitizer."""
+import importlib.util
 import os
 import subprocess
 import sys
@@ -56,8 +62,9 @@ def test_plain_process_uses_linked_hiprtc():
 
 def test_namespace_and_standalone_modules_are_identical(tmp_path):
     # the namespace copy is this ROCm's compiler: its code object is
-    # byte-identical to the standalone test compiler's (a process that never
-    # loads PyTorch) for the same generated source
+    # byte-identical to the one the same code (mk_rtc.cpp behind the
+    # stand-alone driver) builds with the linked hiprtc of a process that
+    # never loads PyTorch, for the same generated source
     import schedcheck as sc
 
     code = r"""
@@ -74,8 +81,10 @@ print(mk.Network(mk.networks.pipeline_network(256)).plan().split("rtc=")[1].spli
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout.split()[-1] == "ns"
     alone = str(tmp_path / "alone.co")
-    t = subprocess.run([sc.rtc_tool(), dump + ".hip", alone], capture_output=True, text=True, timeout=600)
+    t = subprocess.run([sc.rtc_tool(), dump + ".hip", alone], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, MK_HIPRTC="linked"))
     assert t.returncode == 0, t.stdout[-2000:]
+    assert t.stdout.split() == ["linked"], t.stdout  # the driver's linked hiprtc is this ROCm's
     with open(dump, "rb") as f, open(alone, "rb") as g:
         a, b = f.read(), g.read()
     assert a and a == b
@@ -218,3 +227,78 @@ print("RESULT", big.split()[0], small.split()[0], round(time.time() - t, 2), flu
     _, big, small, secs = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT")][-1].split()
     assert big == "tier=compiled", (big, bound)  # D = 256 compiles 4-5 x as long as the small network: past the bound
     assert small == "tier=native" and float(secs) < bound + 1.0, (small, secs, bound)
+
+
+def _stress(tool, mode):
+    """The driver's fixed scenario (tests/native/rtc_compile.cpp stress):
+    concurrent compiles, setenv between compiles, a compile given up at a 0 s
+    bound and the next one not held by it, and exit (in ns mode through the
+    teardown drain, under the compile given up; in linked mode that compile
+    has ended by then, and exit under a running linked compile is not shown).
+    AMD_COMGR_CACHE=0: every compile really compiles.
+
+    The next compile after the one given up is "ns" in ns mode.  In linked
+    mode it is "ns" only if the compile given up had started: hiprtc_run never
+    starts a linked compile whose caller has already gone, and with a 0 s
+    bound the caller goes before the compile thread looks in about one run
+    in eight on an idle host, more often on a busy one.  Nothing is stuck
+    then and "linked" is the right answer, so both are accepted there;
+    test_compile_past_its_bound_does_not_hold_the_next[linked] holds the
+    linked-to-namespace step with a bound of a second or more, by which the
+    compile given up has long started."""
+    e = dict(os.environ, MK_HIPRTC=mode, AMD_COMGR_CACHE="0")
+    r = subprocess.run([tool, "stress"], capture_output=True, text=True, timeout=300, env=e)
+    noise = [ln for ln in r.stderr.splitlines() if not ln.startswith("mk:")]
+    assert r.returncode == 0 and not noise, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    result = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT")]
+    nexts = ["ns", "linked"] if mode == "linked" else ["ns"]
+    assert len(result) == 1 and result[0] in [f"RESULT ok from={mode} next={n}" for n in nexts], r.stdout
+
+
+@pytest.mark.parametrize("mode", ["linked", "ns"])
+def test_driver_stress(mode):
+    import schedcheck as sc
+
+    _stress(sc.rtc_tool(), mode)
+
+
+@pytest.mark.parametrize("mode", ["linked", "ns"])
+def test_driver_stress_sanitized(mode):
+    # the same under AddressSanitizer + UndefinedBehaviorSanitizer, as a
+    # program of its own: a report goes to stderr and fails the exit status
+    import schedcheck as sc
+
+    _stress(sc.rtc_tool(sanitize=True), mode)
+
+
+def test_co_meta_matches_readelf(tmp_path):
+    # the executor's metadata reader (mk_rtc.cpp co_meta) against
+    # llvm-readelf's reading of the same code object's notes
+    import schedcheck as sc
+
+    spec = importlib.util.spec_from_file_location("module_regs", os.path.join(ROOT, "tools", "module_regs.py"))
+    regs = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(regs)
+    code = r"""
+import os, sys
+sys.path[:0] = [{root!r}]
+import misaka_net_amd as mk
+print(mk.Network(mk.networks.example_network()).plan().split()[0])
+"""
+    dump = str(tmp_path / "example.co")
+    r = subprocess.run([sys.executable, "-c", code.format(root=ROOT)], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, MK_JIT_DUMP=dump))
+    assert r.returncode == 0 and r.stdout.split()[-1] == "tier=native", (r.stdout, r.stderr[-2000:])
+    co = str(tmp_path / "driver.co")
+    t = subprocess.run([sc.rtc_tool(), dump + ".hip", co], capture_output=True, text=True, timeout=600)
+    assert t.returncode == 0, t.stdout[-2000:]
+    keys = [".vgpr_count", ".agpr_count", ".sgpr_count", ".private_segment_fixed_size"]
+    m = subprocess.run([sc.rtc_tool(), "meta", co] + keys + [".no_such_key"], capture_output=True, text=True,
+                       timeout=60)
+    assert m.returncode == 0, m.stdout[-2000:]
+    got = dict(ln.split() for ln in m.stdout.splitlines())
+    ref = regs.kernel_meta(co)
+    assert ref["vgpr_count"] > 0, ref  # the notes were found and read
+    for k in keys:
+        assert ref[k[1:]] is not None and int(got[k]) == ref[k[1:]], (k, got, ref)
+    assert int(got[".no_such_key"]) == -1, got

@@ -8,7 +8,7 @@ read its kernel metadata: VGPRs, AGPRs, SGPRs, spills, scratch, LDS.
 
   python tools/module_regs.py [config ...] [--src DIR]   (default: every config)
 
-The same compiler builds the module on the GPU box (mk_exec.hip hiprtc_run),
+The same compiler builds the module on the GPU box (mk_rtc.cpp hiprtc_run),
 so these are the counts the kernel runs with there.
 """
 from __future__ import annotations
