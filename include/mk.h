@@ -429,8 +429,8 @@ int mk_requests_group_device(int device, uint32_t n, const uint32_t *d_ids, size
  * A restore overwrites the listed sessions completely.  A record with
  * held == 1 goes back to the native tier when the block's native_hash is the
  * set's own (and not 0); every other record is restored from its canonical
- * part, and in a native-tier set that session is the interpreter's from then
- * on, as after a hand-off.  So a block can go to another set, another GPU or
+ * part, and in a native-tier set that session is the interpreter's until
+ * promoted (mk_session_promote), as after a hand-off.  So a block can go to another set, another GPU or
  * another tier of the same network at the same stack_cap.
  *
  * Both operations are ordered against every other launch of the set like the
@@ -476,6 +476,39 @@ int mk_session_restore(mk_session *s, const uint32_t *sel, size_t m, const mk_se
  * nothing and leaves its session untouched. */
 int mk_session_restore_device(mk_session *s, const uint32_t *d_sel, size_t m, const mk_session_layout *from,
                               const uint32_t *d_rec, size_t mcols, const uint32_t *d_col, void *stream);
+
+/* ---- promotion: interpreter-held sessions back to the native tier ----------
+ * In a native-tier set a session whose call ran out of its budget slice, or
+ * that was restored from a record's canonical part, is the interpreter's; it
+ * stays there until promoted.  A listed session is ELIGIBLE when the
+ * interpreter holds it and its call is closed: none open, no hand-off of a
+ * launch in flight, so no input or steps pending (io bits 2, 3 and 8-14
+ * clear; pin and csteps count only while a call is open).  An eligible session
+ * that has ended goes back as ended.
+ * A live one goes back when its state is an instance of the entry state of a
+ * superblock a call starts at: the control (every ip, pend, hung, pfull, the
+ * channel bits, the ordinary stacks' depths) agrees exactly and every constant
+ * the compiler built into that superblock's code has its value.  Where several
+ * superblocks match, the one with the LOWEST INDEX is taken, so every build
+ * and the CPU model agree session by session.  Every state that calls,
+ * resumes, resets and restores of such states produce matches; a state left
+ * by mk_session_cancel of an open call may match nothing, and that session
+ * stays on the interpreter (flag 0).  Promotion changes no result: later calls
+ * return what they would have returned, only on the faster tier.  Nothing
+ * promotes by itself.
+ *
+ * Both forms are ordered against every other launch of the set like the
+ * indexed forms; MK_EDEVICE on a set broken by a failed launch.  m == 0 is
+ * MK_OK and launches nothing.  A set on the interpreter's tier (one with remote
+ * peers included) has nowhere to promote to: MK_OK, all flags 0, nothing
+ * launched. */
+/* Host form, synchronous: sel as in the indexed forms (NULL with m == n: every session),
+ * checked, MK_EINVAL before anything is queued.  promoted (nullable) has m bytes,
+ * *count (nullable) the number promoted. */
+int mk_session_promote(mk_session *s, const uint32_t *sel, size_t m, uint8_t *promoted, size_t *count);
+/* Device form, asynchronous on `stream`: d_sel on trust under the indexed contract
+ * (an entry >= n touches nothing and reports 0); d_promoted (nullable) has m bytes. */
+int mk_session_promote_device(mk_session *s, const uint32_t *d_sel, size_t m, uint8_t *d_promoted, void *stream);
 
 void mk_session_free(mk_session *s);
 

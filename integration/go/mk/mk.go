@@ -458,6 +458,30 @@ func (s *Sessions) CallOpen(sel []uint32) ([]bool, error) {
 	return open, nil
 }
 
+// Promote hands the listed instances that the interpreter holds between calls
+// back to the native tier (sel nil: all n) and reports, in list order, which
+// were promoted -- mk_session_promote.  An instance with a call open, one the
+// native tier already holds and one whose state a cancel left outside every
+// call-start state report false and stay as they are.
+func (s *Sessions) Promote(sel []uint32) ([]bool, error) {
+	m := len(sel)
+	if sel == nil {
+		m = s.n
+	}
+	took := make([]bool, m)
+	if m == 0 {
+		return took, nil
+	}
+	raw := make([]uint8, m)
+	if rc := C.mk_session_promote(s.s, selPtr(sel), C.size_t(m), (*C.uint8_t)(unsafe.Pointer(&raw[0])), nil); rc != C.MK_OK {
+		return nil, fmt.Errorf("mk_session_promote: %d", int(rc))
+	}
+	for i, v := range raw {
+		took[i] = v != 0
+	}
+	return took, nil
+}
+
 // RemoteRequest is an outstanding Program.Send / Stack.Push / Stack.Pop of a
 // parked call (mk_remote_req).
 type RemoteRequest struct {

@@ -162,6 +162,8 @@ SIGNATURES = {
     "mk_session_restore_device": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(mk_session_layout), C.c_void_p, C.c_size_t,
                   C.c_void_p, C.c_void_p]),
+    "mk_session_promote": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "mk_session_promote_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "mk_session_reset": (C.c_int, [C.c_void_p]),
     "mk_session_cancel": (C.c_int, [C.c_void_p]),
     "mk_session_plan": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),

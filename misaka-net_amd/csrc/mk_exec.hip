@@ -45,6 +45,7 @@
 #define MK_HD __host__ __device__
 #include "sess_convert.h"
 #include "sess_record.h"
+#include "sess_promote.h"
 #include "sess_stage.h"
 #include "req_group.h"
 
@@ -1651,6 +1652,136 @@ __global__ void __launch_bounds__(kBlock) tis_session_restore_sel(SessParams p, 
     }
 }
 
+// ---- promotion: interpreter-held sessions back to the native tier (sess_promote.h) ----
+// Two kernels on one stream.  The first decides and fills: every block of the
+// grid's y reaches the same verdict for entry t -- it reads the interpreter's
+// arrays, nsb and the maps, none of which this kernel writes -- and writes its
+// share of the instance's register and slot rows (row r belongs to y == r mod
+// gridDim.y): 0, then what the map names, the dynamic stacks' entries among
+// them.  y 0 leaves the verdict in verdict[t].  The second kernel, which runs
+// after every block of the first has read what it needs, hands the instance
+// over: nsb, the hand-off words, the interpreter's words zeroed as a native
+// restore zeroes them (its stack entries, dead above a depth of 0, stay),
+// promoted[t], and sflags[1] down by the wave's count in one atomic.
+constexpr uint32_t kPromoDead = 0xFFFFFFFFu; // verdict: 0 stays, 1 + k live at superblock k, this: ended
+
+struct SessPromoK {
+    SessPromoTab tab;
+    uint32_t *verdict; // [m]
+};
+
+struct SessPromoIn {
+    const SessParams &p;
+    uint64_t i, n;
+    __device__ int32_t ip(int k) const { return p.ip[(uint64_t)k * n + i]; }
+    __device__ int64_t acc(int k) const { return p.acc[(uint64_t)k * n + i]; }
+    __device__ int64_t bak(int k) const { return p.bak[(uint64_t)k * n + i]; }
+    __device__ int32_t pendv(int k) const { return p.pendv[(uint64_t)k * n + i]; }
+    __device__ int32_t port(int q) const { return p.port[(uint64_t)q * n + i]; }
+    __device__ uint64_t pfull() const { return p.pfull[i]; }
+    __device__ uint32_t bits() const { return p.bits[i]; }
+    __device__ bool in_full() const { return p.io[i] & 1u; }
+    __device__ bool out_full() const { return p.io[i] & 2u; }
+    __device__ int32_t in_val() const { return p.in_val[i]; }
+    __device__ int32_t out_val() const { return p.out_val[i]; }
+    __device__ uint32_t depth(int s) const { return (uint32_t)p.sdepth[(uint64_t)s * n + i]; }
+    __device__ int32_t entry(int s, uint32_t j) const { return p.stk[((uint64_t)s * p.stack_cap + j) * n + i]; }
+};
+
+// this block's share of the register and slot rows of instance i
+struct SessPromoOut {
+    const SessSnapK &q;
+    const SessPromoIn &in;
+    uint64_t i, n;
+    uint32_t y, gy;
+    __device__ void reg(uint32_t r, int64_t v)
+    {
+        if (r % gy == y && r < q.nregs) q.regs[(uint64_t)r * n + i] = v;
+    }
+    __device__ void slot(uint32_t s, int32_t v)
+    {
+        if (s % gy == y && s < q.nslots) q.slots[(uint64_t)s * n + i] = v;
+    }
+    __device__ void dyn(int s, uint32_t base, uint32_t d)
+    {
+        for (uint32_t j = (y + gy - base % gy) % gy; j < d; j += gy)
+            if (base + j < q.nslots) q.slots[(uint64_t)(base + j) * n + i] = in.entry(s, j);
+    }
+};
+
+__global__ void __launch_bounds__(kBlock) tis_session_promote_sel(SessParams p, SessSnapK q, SessPromoK w,
+                                                                  const uint32_t *sel, uint64_t first, uint64_t m)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= m) return;
+    const uint64_t i = sel ? (uint64_t)sel[t] : first + t, n = p.n;
+    uint32_t v = 0u;
+    const SessPromoIn in{p, i, n};
+    if (i < n && q.nsb[i] == kSessT1) {
+        const uint32_t io = p.io[i];
+        // the call closed (bits 2, 3: with them clear pin and csteps are stale words of the last
+        // parked call, nothing pending) and nothing of a launch's hand-off in flight (8-14)
+        if (!(io & 0x7F0Cu)) {
+            if (io & 0xF0u) {
+                v = kPromoDead;
+            } else {
+                const int64_t k = sess_promote_find(p.nprog, p.nstack, p.stack_cap, w.tab, q.hdr, q.map, q.dyn_base, in);
+                if (k >= 0) v = 1u + (uint32_t)k;
+            }
+        }
+    }
+    if (blockIdx.y == 0) w.verdict[t] = v;
+    if (!v) return;
+    const uint32_t y = blockIdx.y, gy = gridDim.y;
+    for (uint64_t r = y; r < q.nregs; r += gy) q.regs[r * n + i] = 0;
+    for (uint64_t r = y; r < q.nslots; r += gy) q.slots[r * n + i] = 0;
+    if (v == kPromoDead) return;
+    const SessMapHdr h = q.hdr[v - 1u];
+    SessPromoOut o{q, in, i, n, y, gy};
+    sess_promote_fill(p.nprog, p.nstack, h, q.map + h.off, q.dyn_base, in, o);
+}
+
+__global__ void __launch_bounds__(kBlock) tis_session_promote_commit(SessParams p, SessSnapK q, SessPromoK w,
+                                                                     const uint32_t *sel, uint64_t first, uint64_t m,
+                                                                     uint8_t *promoted)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t n = p.n;
+    uint64_t i = n;
+    uint32_t v = 0u;
+    if (t < m) {
+        i = sel ? (uint64_t)sel[t] : first + t;
+        v = i < n ? w.verdict[t] : 0u;
+        if (promoted) promoted[t] = v ? (uint8_t)1 : (uint8_t)0;
+    }
+    if (v) {
+        for (int k = 0; k < p.nprog; ++k) {
+            p.acc[(uint64_t)k * n + i] = 0;
+            p.bak[(uint64_t)k * n + i] = 0;
+            p.ip[(uint64_t)k * n + i] = 0;
+            p.pendv[(uint64_t)k * n + i] = 0;
+            p.xst[(uint64_t)k * n + i] = 0u;
+            p.xval[(uint64_t)k * n + i] = 0;
+            for (int d = 0; d < 4; ++d) p.port[(uint64_t)(k * 4 + d) * n + i] = 0;
+        }
+        for (int k = 0; k < p.nstack; ++k) p.sdepth[(uint64_t)k * n + i] = 0;
+        p.pfull[i] = 0ull;
+        p.bits[i] = 0u;
+        p.io[i] = 0u;
+        p.in_val[i] = 0;
+        p.out_val[i] = 0;
+        p.pin[i] = 0;
+        p.csteps[i] = 0u;
+        q.nsb[i] = v == kPromoDead ? kSessDead : 2u * (v - 1u);
+        q.hand_sb[i] = 0u;
+        q.hand_steps[i] = 0u;
+        q.hand_call[i] = 0u;
+    }
+    // the interpreter's count: one atomic per wave, not one per instance (no thread has left: lane 0 is here)
+    const unsigned long long took = __ballot(v != 0u);
+    if (took && (threadIdx.x & 63u) == 0u) atomicSub(&q.sflags[1], (uint32_t)__popcll(took));
+}
+
 // Native sessions handed off in this launch (MK_SS_HAND: a call's budget
 // slice ends inside a superblock) become interpreter sessions: the state
 // map of that superblock's entry (tis_sched.h SessMapHdr, from the schedule
@@ -3015,6 +3146,13 @@ struct mk_session {
     std::vector<mk::SessMapHdr> h_hdr;
     std::vector<mk::SessSrcDev> h_rec;
     std::vector<int64_t> h_dyn_base;
+    // promotion (sess_promote.h): the call-start superblocks by control hash,
+    // the compiler's lower bounds of the dynamic stacks' depths beside the
+    // maps, and the verdicts between the two kernels of a promote
+    uint64_t *promo_hash = nullptr;
+    uint32_t *promo_sb = nullptr, *promo_verdict = nullptr;
+    uint8_t *promo_lo = nullptr;
+    uint32_t promo_count = 0;
     // a restore may have given the interpreter sessions of a set whose calls
     // never hand off: its pass is then launched all the same
     bool interp_may_hold = false;
@@ -3191,6 +3329,11 @@ int session_native(mk_session *s)
     std::vector<SessMapHdr> hdr;
     std::vector<SessSrcDev> rec;
     build_sess_map(P, s->nprog, s->nstack, hdr, rec);
+    std::vector<uint8_t> lo;
+    std::vector<uint64_t> promo_hash;
+    std::vector<uint32_t> promo_sb;
+    build_sess_lo(P, s->nstack, lo);
+    sess_promote_table(s->nprog, s->nstack, hdr, rec, P.dyn_base.data(), promo_hash, promo_sb);
     const size_t N = s->n ? s->n : 1;
     size_t lane_bytes = 0;
     // first over nothing, for the size, then over the allocation
@@ -3208,6 +3351,10 @@ int session_native(mk_session *s)
         s->rec = k.take<SessSrcDev>(rec.size());
         s->dyn_base = k.take<int64_t>(std::max<size_t>(P.dyn_base.size(), 1));
         s->pre = k.take<uint32_t>((hdr.size() + 31) / 32 + 1);
+        s->promo_hash = k.take<uint64_t>(std::max<size_t>(promo_hash.size(), 1));
+        s->promo_sb = k.take<uint32_t>(std::max<size_t>(promo_sb.size(), 1));
+        s->promo_lo = k.take<uint8_t>(std::max<size_t>(lo.size(), 1));
+        s->promo_verdict = k.take<uint32_t>(N);
         return k.at;
     };
     const size_t total = carve(nullptr);
@@ -3228,8 +3375,13 @@ int session_native(mk_session *s)
                              hipSuccess) ||
         (!P.dyn_base.empty() &&
          hipMemcpy(s->dyn_base, P.dyn_base.data(), P.dyn_base.size() * 8, hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(s->pre, s->h_pre.data(), s->h_pre.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        hipMemcpy(s->pre, s->h_pre.data(), s->h_pre.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        (!promo_sb.empty() &&
+         (hipMemcpy(s->promo_hash, promo_hash.data(), promo_hash.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(s->promo_sb, promo_sb.data(), promo_sb.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) ||
+        (!lo.empty() && hipMemcpy(s->promo_lo, lo.data(), lo.size(), hipMemcpyHostToDevice) != hipSuccess))
         return MK_EDEVICE;
+    s->promo_count = (uint32_t)promo_sb.size();
     s->h_hdr = std::move(hdr);
     s->h_rec = std::move(rec);
     s->h_dyn_base = P.dyn_base;
@@ -3697,6 +3849,33 @@ int restore_launch(mk_session *s, const uint32_t *d_sel, uint64_t first, uint64_
                            0, st, nullptr, done, 0) != hipSuccess)
         return MK_EDEVICE;
     if (may_hold) s->interp_may_hold = true; // a canonical restore hands its session to the interpreter
+    return MK_OK;
+}
+
+// Queues the promotion of m entries (sessions d_sel[t], or first + t; m <= n) on
+// `st`: the deciding and filling kernel, its y sized so that a block writes
+// about 16 of an instance's register and slot rows, then the hand-over, which
+// records `done`.  Native-tier sets only.
+int promote_launch(mk_session *s, const uint32_t *d_sel, uint64_t first, uint64_t m, uint8_t *d_promoted,
+                   hipStream_t st, hipEvent_t done, bool *queued)
+{
+    unsigned blocks;
+    if (!sel_grid(m, &blocks)) return MK_ELIMIT;
+    SessParams p = s->p;
+    SessSnapK q = session_snapk(s, false);
+    SessPromoK w{SessPromoTab{s->promo_hash, s->promo_sb, s->promo_count, s->promo_lo}, s->promo_verdict};
+    const uint64_t rows = (uint64_t)s->nregs + s->nslots;
+    const unsigned gy = (unsigned)std::min<uint64_t>(std::max<uint64_t>((rows + 15) / 16, 1), 64);
+    void *a1[] = {(void *)&p, (void *)&q, (void *)&w, (void *)&d_sel, (void *)&first, (void *)&m};
+    if (hipExtLaunchKernel(reinterpret_cast<void *>(&tis_session_promote_sel), dim3(blocks, gy), dim3(kBlock), a1, 0, st,
+                           nullptr, nullptr, 0) != hipSuccess)
+        return MK_EDEVICE;
+    if (queued) *queued = true;
+    void *a2[] = {(void *)&p,     (void *)&q, (void *)&w,         (void *)&d_sel,
+                  (void *)&first, (void *)&m, (void *)&d_promoted};
+    if (hipExtLaunchKernel(reinterpret_cast<void *>(&tis_session_promote_commit), dim3(blocks), dim3(kBlock), a2, 0, st,
+                           nullptr, done, 0) != hipSuccess)
+        return MK_EDEVICE;
     return MK_OK;
 }
 
@@ -4515,6 +4694,52 @@ int mk_session_restore_device(mk_session *s, const uint32_t *d_sel, size_t m, co
     if (m == 0) return MK_OK;
     return mk::session_on_stream(s, stream, [&](hipStream_t st, bool *, hipEvent_t done) {
         return mk::restore_launch(s, d_sel, 0, m, mk::layout_native(s, from), true, d_rec, mcols, d_col, st, done);
+    });
+}
+
+int mk_session_promote(mk_session *s, const uint32_t *sel, size_t m, uint8_t *promoted, size_t *count)
+{
+    if (!s) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (sel ? !mk::sel_valid(s, sel, m) : m != s->n) return MK_EINVAL; // a null list: every session, m == n
+    if (s->broken) return MK_EDEVICE;
+    if (count) *count = 0;
+    if (m == 0) return MK_OK;
+    if (promoted) memset(promoted, 0, m);
+    if (!s->native) return MK_OK; // the interpreter's tier: nowhere to promote to
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    uint32_t *d_sel;
+    size_t o_flag = m; // m bytes behind the list
+    if (int rc = mk::session_stage_sel(s, sel, m, &o_flag, &d_sel)) return rc;
+    uint8_t *d_flag = (uint8_t *)s->d_stage + o_flag;
+    if (int rc = mk::promote_launch(s, d_sel, 0, m, d_flag, s->stream, nullptr, nullptr)) return rc;
+    if (hipMemcpyAsync((char *)s->h_stage + o_flag, d_flag, m, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipStreamSynchronize(s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    const uint8_t *f = (const uint8_t *)s->h_stage + o_flag;
+    if (promoted) memcpy(promoted, f, m);
+    if (count)
+        for (size_t t = 0; t < m; t++) *count += f[t];
+    return MK_OK;
+}
+
+int mk_session_promote_device(mk_session *s, const uint32_t *d_sel, size_t m, uint8_t *d_promoted, void *stream)
+{
+    if (!s) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (m > s->n || (!d_sel && m != s->n)) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (m == 0) return MK_OK;
+    if (!s->native) { // all zeroes, and nothing of the set is touched: no ordering against its launches
+        mk::DeviceGuard g(s->device);
+        if (d_promoted &&
+            hipMemsetAsync(d_promoted, 0, m, stream ? (hipStream_t)stream : s->stream) != hipSuccess)
+            return MK_EDEVICE;
+        return MK_OK;
+    }
+    return mk::session_on_stream(s, stream, [&](hipStream_t st, bool *queued, hipEvent_t done) {
+        return mk::promote_launch(s, d_sel, 0, m, d_promoted, st, done, queued);
     });
 }
 

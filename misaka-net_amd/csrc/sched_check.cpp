@@ -18,6 +18,7 @@
 #include "tis_sched.h"
 #include "sess_convert.h"
 #include "sess_record.h"
+#include "sess_promote.h"
 #include "sess_stage.h"
 
 namespace {
@@ -217,6 +218,10 @@ struct SessEmu {
     std::vector<uint8_t> state;     // 0 live, 1 ended (stack overflow), 2 handed off
     std::vector<uint32_t> hand_sb;  // superblock of the hand-off
     std::vector<uint32_t> hand_steps;
+    // promotion (sess_promote.h): Ctl::lo beside the map, the call-start superblocks by control hash
+    std::vector<uint8_t> lo;
+    std::vector<uint64_t> ptab_hash;
+    std::vector<uint32_t> ptab_sb;
 };
 
 void *mkc_sess_new(void *hv, uint32_t cap, uint32_t n, char *why, size_t why_len)
@@ -235,6 +240,8 @@ void *mkc_sess_new(void *hv, uint32_t cap, uint32_t n, char *why, size_t why_len
     e->S = h->net.uses_stacks ? h->net.nstack : 0;
     e->cap = cap;
     mk::build_sess_map(e->P, e->N, e->S, e->hdr, e->rec);
+    mk::build_sess_lo(e->P, e->S, e->lo);
+    mk::sess_promote_table(e->N, e->S, e->hdr, e->rec, e->P.dyn_base.data(), e->ptab_hash, e->ptab_sb);
     e->R.assign(n, std::vector<int64_t>(e->P.nregs, (int64_t)0x5A5A5A5A5A5A5A5All));
     e->slots.assign(n, {});
     e->sb.assign(n, 0);
@@ -488,6 +495,79 @@ int mkc_sess_copy(void *ev, size_t dst, size_t src)
     e->hand_sb[dst] = e->hand_sb[src];
     e->hand_steps[dst] = e->hand_steps[src];
     return 0;
+}
+
+namespace {
+struct FlatIn {
+    const orc_flat &f;
+    const int32_t *entries;
+    uint32_t cap;
+    int32_t ip(int n) const { return f.ip[n]; }
+    int64_t acc(int n) const { return f.acc[n]; }
+    int64_t bak(int n) const { return f.bak[n]; }
+    int32_t pendv(int n) const { return f.pendv[n]; }
+    int32_t port(int q) const { return f.port[q]; }
+    uint64_t pfull() const { return f.pfull; }
+    uint32_t bits() const { return (f.pend & 0xffffu) | (f.hung << 16); }
+    bool in_full() const { return f.in_full != 0; }
+    bool out_full() const { return f.out_full != 0; }
+    int32_t in_val() const { return f.in_val; }
+    int32_t out_val() const { return f.out_val; }
+    uint32_t depth(int s) const { return f.depth[s]; }
+    int32_t entry(int s, uint32_t j) const { return entries[(size_t)s * cap + j]; }
+};
+struct EmuFill {
+    std::vector<int64_t> &R;
+    std::unordered_map<uint32_t, int32_t> &slots;
+    const FlatIn &in;
+    void reg(uint32_t r, int64_t v) { R.at(r) = v; }
+    void slot(uint32_t q, int32_t v) { slots[q] = v; }
+    void dyn(int s, uint32_t base, uint32_t d)
+    {
+        for (uint32_t j = 0; j < d; j++) slots[base + j] = in.entry(s, j);
+    }
+};
+} // namespace
+
+// Promotion (sess_promote.h) of the canonical state f, a live instance between
+// calls in the interpreter's terms, into session dst: the superblock it is an
+// instance of, or -1 when the state has a call open (deposited, pin, pos,
+// changed or csteps set) or matches no call-start superblock; dst is then
+// untouched.  On a match dst is live at that superblock, its named registers
+// and slots filled.  What the map does not name is garbage (registers) or
+// absent (slots) here, where the GPU writes 0: a register or slot the fill
+// forgot then shows in the next call.
+int mkc_sess_promote(void *ev, size_t dst, const orc_flat *f, const int32_t *entries)
+{
+    auto *e = (SessEmu *)ev;
+    if (dst >= e->sb.size() || !f) return -1;
+    if (f->deposited || f->pin || f->pos || f->changed || f->csteps) return -1;
+    for (int s = 0; s < e->S; s++)
+        if (f->depth[s] > e->cap) return -1;
+    const FlatIn in{*f, entries, e->cap};
+    const mk::SessPromoTab tab{e->ptab_hash.data(), e->ptab_sb.data(), (uint32_t)e->ptab_sb.size(), e->lo.data()};
+    const int64_t k = mk::sess_promote_find(e->N, e->S, e->cap, tab, e->hdr.data(), e->rec.data(),
+                                            e->P.dyn_base.data(), in);
+    if (k < 0) return -1;
+    e->R[dst].assign(e->P.nregs, (int64_t)0x5A5A5A5A5A5A5A5All);
+    e->slots[dst].clear();
+    EmuFill o{e->R[dst], e->slots[dst], in};
+    const mk::SessMapHdr &h = e->hdr[(size_t)k];
+    mk::sess_promote_fill(e->N, e->S, h, e->rec.data() + h.off, e->P.dyn_base.data(), in, o);
+    e->sb[dst] = 2u * (uint32_t)k;
+    e->state[dst] = 0;
+    e->hand_sb[dst] = 0;
+    e->hand_steps[dst] = 0;
+    return (int)k;
+}
+
+// Kind of location X (the compiler's order: ACC(n), BAK(n), PORT(q), PENDV(n),
+// INL, OUTL, DEP(s), CIN) in superblock k's map: 0 dead, 1 constant, 2 register; -1 out of range.
+int mkc_sess_loc_kind(void *ev, uint32_t k, uint32_t X)
+{
+    auto *e = (SessEmu *)ev;
+    if (k >= e->hdr.size() || X >= (uint32_t)(7 * e->N + 2 + e->S + 1)) return -1;
+    return (int)e->rec[e->hdr[k].off + (uint32_t)e->N + X].kind;
 }
 
 // The session lane of the native tier (tis_jit.h jit_session_lane) for the

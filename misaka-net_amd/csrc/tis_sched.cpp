@@ -1515,6 +1515,9 @@ bool Compiler::run(SchedProgram &out, std::string &why)
             m.pos = e.ctl.pos;
             m.changed = e.ctl.changed;
             m.pre = e.ctl.pre;
+            m.lo.assign(S_, 0);
+            for (int s = 0; s < S_; s++)
+                if (dyn(s)) m.lo[s] = e.ctl.lo[s];
             m.loc.resize(L0_);
             for (int X = 0; X < L0_; X++) {
                 const Val &v = e.loc[X];
@@ -1685,6 +1688,13 @@ void build_sess_map(const SchedProgram &p, int nprog, int nstack, std::vector<Se
             for (size_t d = 0; d < k; d++) put(m.stk[s][d]);
         }
     }
+}
+
+void build_sess_lo(const SchedProgram &p, int nstack, std::vector<uint8_t> &lo)
+{
+    lo.assign(p.smap.size() * (size_t)nstack, 0);
+    for (size_t k = 0; k < p.smap.size(); k++)
+        for (size_t s = 0; s < p.smap[k].lo.size() && s < (size_t)nstack; s++) lo[k * (size_t)nstack + s] = p.smap[k].lo[s];
 }
 
 std::string sched_disasm(const SchedProgram &p)

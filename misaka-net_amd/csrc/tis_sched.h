@@ -101,6 +101,9 @@ struct SessEntry {
     bool pre = false;     // the call's round-start checks are still to run
     std::vector<SessSrc> loc;              // every location, in the compiler's order
     std::vector<std::vector<SessSrc>> stk; // ordinary stacks: their entries, bottom first
+    // dynamic stacks: the depth the superblock's code takes for granted (0 or 1: a POP it makes without a
+    // check); part of the compiler's state key that the locations do not show.  Read by sess_promote.h.
+    std::vector<uint8_t> lo;
 };
 
 // Device form of the session state map (SchedProgram::smap), one header per
@@ -126,6 +129,8 @@ static_assert(sizeof(SessMapHdr) == 24, "SessMapHdr must be 24 bytes");
 struct SchedProgram;
 void build_sess_map(const SchedProgram &p, int nprog, int nstack, std::vector<SessMapHdr> &hdr,
                     std::vector<SessSrcDev> &rec);
+// Beside the map: SessEntry::lo of every superblock, [superblock][nstack] (0 for ordinary stacks).
+void build_sess_lo(const SchedProgram &p, int nstack, std::vector<uint8_t> &lo);
 
 struct SchedProgram {
     std::vector<UOp> code;

@@ -616,7 +616,7 @@ class SessionSet:
         without ``take``).  The snapshot may come from another set, GPU or
         tier of the same network and stack_cap; a record goes back to the
         native tier only in a set running the same native module, otherwise
-        the interpreter holds that instance from then on.  ValueError, with
+        the interpreter holds that instance until promoted.  ValueError, with
         nothing changed, for a layout of another network or a record out of
         range."""
         sel = self._index(index) if index is not None else None
@@ -674,6 +674,29 @@ class SessionSet:
         self._layout_fits(layout)
         N.check(N.lib().mk_session_restore_device(self._h, index_ptr, self.n if m is None else m, C.byref(layout),
                                                   rec_ptr, mcols, take_ptr, stream), "mk_session_restore_device")
+
+    # ---- promotion (include/mk.h: interpreter-held instances back to the native tier) ----
+    def promote(self, index=None) -> np.ndarray:
+        """Hand every instance the interpreter holds between calls back to the
+        native tier, or the listed ones only; bool flags in list order, True
+        where the instance was promoted (mk_session_promote).  An instance
+        with a call open, one the native tier already holds, and one whose
+        state a cancel left outside every call-start state report False and
+        stay as they are.  Later calls return what they would have anyway."""
+        sel = self._index(index) if index is not None else None
+        m = self.n if sel is None else sel.size
+        flags = np.zeros(m, np.uint8)
+        N.check(N.lib().mk_session_promote(self._h, _ptr(sel), m, _ptr(flags), None), "mk_session_promote")
+        return flags.astype(bool)
+
+    def promote_device(self, flags_ptr, *, stream=None, index_ptr=None, m=None):
+        """:meth:`promote` on device arrays, asynchronous on ``stream``:
+        ``flags_ptr`` (a device uint8 array of ``m`` entries, or None) takes
+        the flags; ``index_ptr`` and ``m`` as in :meth:`compute_device`."""
+        if (index_ptr is None) != (m is None):
+            raise ValueError("index_ptr and m go together")
+        N.check(N.lib().mk_session_promote_device(self._h, index_ptr, self.n if m is None else m, flags_ptr, stream),
+                "mk_session_promote_device")
 
     def close(self):
         if getattr(self, "_h", None):
