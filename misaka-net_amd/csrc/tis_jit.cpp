@@ -1323,7 +1323,8 @@ void emit_self_loop(const OpWriter &w, const Graph &g, uint32_t v, size_t gpc, s
     // of 2 uf decrements while some lane still needs more than uf, then the
     // uf chunks -- half the exit tests on long trips, and no more idle
     // iterations than uf chunks alone (a 2 uf chunk starts only when a lane
-    // needs over uf of them).  MK_JIT_SAT_TIER=0: uf chunks only.
+    // needs over uf of them).  Always on: the MK_JIT_SAT_TIER knob that
+    // turned it off went in round 6.
     auto emit_sat_tier = [&](const char *c) {
         e.line("    while (more && T32 - it >= %uu && MK_KEEP(%s > %d, need)) {", 2 * uf, c, uf);
         e.line("    it += %uu;", 2 * uf);
@@ -2839,7 +2840,8 @@ std::string module_prelude(JitShape shape, const JitLimits &lim, uint32_t pool, 
         e.line("#define MK_T() __builtin_amdgcn_s_memtime()");
     }
     e.line("#define MK_ALL(p) (__ballot(!(p)) == 0ull)");
-    // MK_JIT_PRIO=1: waves in a self-loop's phases at priority 0, after a
+    // Wave priority, always on in machine modules (the MK_JIT_PRIO knob went
+    // in round 6): waves in a self-loop's phases at priority 0, after a
     // loop (dispatch rounds, latency-bound) at 1, so the issue arbiter
     // prefers them over the loops' throughput-bound VALU streams (a wave
     // starts at 0)

@@ -14,7 +14,8 @@ from misaka_net_amd import _native as N
 from oracle import pyoracle as po
 from tisgen import (ROT_BUDGETS, ROT_CAPS, deep_seed_kwargs, deep_stack_inputs, deep_stack_network, loop_cases,
                     random_network, rotated_seed_kwargs, rotated_stack_inputs, rotated_stack_loop_network,
-                    rotated_stack_loop_programs, stack_loop_network)
+                    rotated_stack_loop_programs, self_loop_budgets, self_loop_gpu_programs, self_loop_inputs,
+                    self_loop_meta, stack_loop_network)
 
 pytestmark = pytest.mark.gpu
 
@@ -153,6 +154,71 @@ def test_rotated_stack_networks_bit_exact(gpu, seed, mode):
     kw = rotated_seed_kwargs(seed)
     got = mk.Network(rows).compute_batch(xs, mode=_m(mode), **kw)
     assert_same(got, oracle(rows, xs, **kw), f"seed {seed}")
+
+
+# ---- the self-loop family (tisgen.self_loop_programs) on the hardware -----------
+# What the CPU lane test cannot see: the inline asm of the flag, bump and
+# saturating macros (MAD24 by steps up to +-8388607), the unguarded iterations
+# T taken from the wave's largest step count, and waves whose lanes disagree
+# about the 2^30 range check of the narrow phase.  48 rows that reach every
+# form and every step, 2,048 lanes (two sort tiles), every budget of the row
+# on one module.  All rows on the default path and in input order
+# ("plain-order": the tile sort off, so a wave is 64 neighbours of the input
+# and mixes values); twelve of them also under the variants of
+# test_loop_phases_bit_exact and with one lane per thread, asm blocks of 8,
+# the counter form off and chunks of 3.
+SL_N = 2048
+SL_ENV = {
+    "auto": {},
+    "plain-order": {"MK_JIT_SHAPE": "machine", "MK_JIT_TILE_SORT": "0"},
+    "machine-early-exit": {"MK_JIT_SHAPE": "machine", "MK_JIT_POLICY": "8,12,16"},
+    "pool64": {"MK_JIT_SHAPE": "machine", "MK_JIT_POOL": "64"},
+    "k2": {"MK_JIT_SHAPE": "machine", "MK_JIT_POOL": "2"},
+    "pair0": {"MK_JIT_PAIR": "0"},
+    "satblock8": {"MK_JIT_SAT_BLOCK": "8"},
+    "count0": {"MK_JIT_SAT_COUNT": "0"},
+    "unroll3": {"MK_JIT_LOOP_UNROLL": "3"},
+}
+_SL_FEW = {row[0] for row in self_loop_gpu_programs(few=True)}
+SL_CASES = [(row[0], variant) for row in self_loop_gpu_programs()  # a row's variants side by side: they share its reference
+            for variant in (SL_ENV if row[0] in _SL_FEW else ("auto", "plain-order"))]
+
+
+@functools.lru_cache(maxsize=2)
+def _self_loop_reference(label):
+    """(nodes, inputs, {budget: the oracle's out, status, steps})"""
+    nodes = {row[0]: row[1] for row in self_loop_gpu_programs()}[label]
+    xs = np.asarray(self_loop_inputs(label, SL_N), np.int64)
+    net = po.OracleNet(nodes)
+    return nodes, xs, {b: net.compute_batch(xs, threads=THREADS, budget=b) for b in self_loop_budgets(label)}
+
+
+def _assert_waves_are_mixed(label, xs, steps):
+    """A property of the fixture, not luck: in input order some wave holds
+    lanes on both sides of the narrow phase's range check, and some wave's
+    trip counts (the oracle's steps at the largest budget) lie further apart
+    than two unguarded chunks."""
+    m = self_loop_meta(label)
+    at_loop = np.abs(xs.reshape(-1, 64) * m["mult"])  # the register when the loop is entered
+    assert ((at_loop <= 2**30).any(axis=1) & (at_loop > 2**30).any(axis=1)).any(), label
+    body, _, exit_ = label.split("/") if not label.startswith("chain/") else ("chain", "", "")
+    if body == "bump" and exit_ in ("JEZ", "iJNZ"):
+        return  # the loop stays only while its register is 0: two trips at the most
+    waves = steps.astype(np.int64).reshape(-1, 64)
+    assert ((waves.max(axis=1) - waves.min(axis=1)) > (2 * m["uf"] + 1) * m["inc"] + 8).any(), label
+
+
+@pytest.mark.parametrize("label,variant", SL_CASES)
+def test_self_loop_family_bit_exact(gpu, monkeypatch, label, variant):
+    for name, value in SL_ENV[variant].items():
+        monkeypatch.setenv(name, value)
+    nodes, xs, refs = _self_loop_reference(label)
+    if variant == "plain-order":
+        _assert_waves_are_mixed(label, xs, refs[6000][2])
+    net = mk.Network(nodes)
+    assert net.plan().startswith("tier=native") and "shape=machine" in net.plan(), net.plan()
+    for budget, ref in refs.items():
+        assert_same(net.compute_batch(xs, budget=budget), ref, f"{label} {variant} budget {budget}")
 
 
 # Both stack-slot layouts of the heavy kernel (wave-blocked / lane-major),
@@ -1081,20 +1147,13 @@ def test_machine_input_order_is_transparent(gpu, monkeypatch, kind):
         rows = random_network(seed)
         cases.append((f"seed{seed}", rows, (N.MK_GEN_FULL, 0)))
     # "1": global order by value (MK_JIT_ORDER); "0": the default tile-sorted
-    # kernel; "dyn" / "snake": the tile-sorted kernel with its chunks taken by
-    # free waves / in snake order (MK_JIT_TS_DYN); "plain": input order
-    # (MK_JIT_TILE_SORT=0)
-    variants = {"1": ("1", "1", None), "0": ("0", "1", None), "dyn": ("0", "1", "1"), "snake": ("0", "1", "0"),
-                "plain": ("0", "0", None)}
+    # kernel; "plain": input order (MK_JIT_TILE_SORT=0)
+    variants = {"1": ("1", "1"), "0": ("0", "1"), "plain": ("0", "0")}
     for label, nodes, gen in cases:
         res = {}
-        for order, (o, ts, dyn) in variants.items():
+        for order, (o, ts) in variants.items():
             monkeypatch.setenv("MK_JIT_ORDER", o)
             monkeypatch.setenv("MK_JIT_TILE_SORT", ts)
-            if dyn is None:
-                monkeypatch.delenv("MK_JIT_TS_DYN", raising=False)
-            else:
-                monkeypatch.setenv("MK_JIT_TS_DYN", dyn)
             net = mk.Network(nodes)
             if "shape=machine" not in net.plan():
                 monkeypatch.setenv("MK_JIT_SHAPE", "machine")
@@ -1107,7 +1166,7 @@ def test_machine_input_order_is_transparent(gpu, monkeypatch, kind):
                 res[order] = _device_run(net, n, in_tensor=xs.to(torch.int32).cuda(), in_kind=N.MK_IN_I32)
             else:
                 res[order] = _device_run(net, n, in_tensor=xs.cuda(), in_kind=N.MK_IN_I64)
-        for k in ("0", "dyn", "snake", "plain"):
+        for k in ("0", "plain"):
             for a, b in zip(res["1"], res[k]):
                 assert np.array_equal(a, b), (label, k)
         ref = oracle(nodes, po.gen_inputs(SEED, n, kind=gen[0], mask=gen[1])[-3000:])

@@ -8,6 +8,7 @@ function inside the hiprtc-compiled kernel (tests/test_gpu_parity.py, mode
 needs no GPU)."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -19,7 +20,8 @@ from oracle import pyoracle as po
 import schedcheck as sc
 from tisgen import (census_classes, deep_seed_kwargs, deep_stack_inputs, deep_stack_network, deep_stack_peaks,
                     stack_loop_network, loop_cases, random_network, rotated_seed_kwargs, rotated_stack_loop_cases,
-                    rotated_stack_loop_network)
+                    rotated_stack_loop_network, SELF_LOOP_STEPS, SELF_LOOP_EXITS, self_loop_budgets,
+                    self_loop_gpu_programs, self_loop_inputs, self_loop_meta, self_loop_programs)
 
 SEED = 0x4D49534B41
 
@@ -87,10 +89,13 @@ def check_cases(tmp_path, cases, machine=False):
     """cases: [(label, nodes, xs, kw)] -- every case compiled and compared.
     ``machine``: the resumable (machine-shape) lane for every case."""
     srcs, keep, lane = [], [], {}
+    emitted, nets = {}, {}  # cases that share their nodes object (a budget sweep): one lane source, one oracle net
     for label, nodes, xs, kw in cases:
+        key = (id(nodes), kw.get("stack_cap"), kw.get("stop_on_output", False))
         try:
-            src, ns = sc.jit_lane(nodes, stack_cap=kw.get("stack_cap"), stop_on_output=kw.get("stop_on_output", False),
-                                  machine=machine)
+            if key not in emitted:
+                emitted[key] = sc.jit_lane(nodes, stack_cap=key[1], stop_on_output=key[2], machine=machine)
+            src, ns = emitted[key]
         except sc.NotCompiled:
             continue  # tier 1 handles it; covered elsewhere
         if (src, ns) not in lane:  # cases that differ in the budget only share a lane
@@ -101,7 +106,9 @@ def check_cases(tmp_path, cases, machine=False):
     lib = build_lanes(srcs, str(tmp_path / "lanes"))
     for label, nodes, xs, kw, i in keep:
         got = run_lane(lib, i, xs, kw.get("budget") or (1 << 20))
-        ref = po.OracleNet(nodes).compute_batch(xs, **kw)
+        if id(nodes) not in nets:
+            nets[id(nodes)] = po.OracleNet(nodes)
+        ref = nets[id(nodes)].compute_batch(xs, **kw)
         bad = np.nonzero((got[0] != ref[0]) | (got[1] != ref[1]) | (got[2] != ref[2]))[0]
         assert not bad.size, (label, int(bad[0]), [g[bad[0]] for g in got], [r[bad[0]] for r in ref])
     return [k[0] for k in keep]
@@ -158,6 +165,170 @@ def test_loop_phases(tmp_path):
     # every path of the machine shape's self-loops (tisgen.loop_cases)
     cases = [(lbl, nodes, np.asarray(xs, np.int64), kw) for lbl, nodes, xs, kw in loop_cases()]
     assert len(check_cases(tmp_path, cases, machine=True)) == len(cases)
+
+
+# ---- the self-loop family (tisgen.self_loop_programs) ---------------------------
+# Every step, exit test and body that moves emit_self_loop to another form, at
+# every budget that walks the unguarded iterations T across its chunk
+# boundaries.  Lane by lane here (MK_KEEP and MK_ALL are the lane's own, the
+# flag and bump macros plain C); tests/test_gpu_parity.py runs the curated
+# rows on the hardware, where the asm, the wave-uniform T and the waves whose
+# lanes disagree about the 2^30 range check are.
+
+SL_LANES = 64
+SL_BLOCK = 78  # programs per block of test_self_loop_family
+SL_KNOBS = {"count0": {"MK_JIT_SAT_COUNT": "0"}, "unroll1": {"MK_JIT_LOOP_UNROLL": "1"},
+            "unroll3": {"MK_JIT_LOOP_UNROLL": "3"}, "unroll64": {"MK_JIT_LOOP_UNROLL": "64"}}
+
+
+def _self_loop_cases(rows, uf=None):
+    cases = []
+    for label, nodes, _ in rows:
+        xs = np.asarray(self_loop_inputs(label, SL_LANES), np.int64)
+        cases += [(f"{label} budget {b}", nodes, xs, {"budget": b}) for b in self_loop_budgets(label, uf=uf)]
+    return cases
+
+
+@pytest.mark.parametrize("which", [f"all-{b}" for b in range((len(self_loop_programs()) + SL_BLOCK - 1) // SL_BLOCK)] +
+                         [f"{k}-gpu" for k in SL_KNOBS])
+def test_self_loop_family(tmp_path, monkeypatch, which):
+    # all-<block>: every row at every budget, default knobs; <knob>-gpu: the
+    # GPU's rows without the counter form, and with other chunk sizes (the
+    # budgets then walk that chunk size)
+    knob, part = which.split("-")
+    uf = None
+    if knob == "all":
+        rows = self_loop_programs()[int(part) * SL_BLOCK:(int(part) + 1) * SL_BLOCK]
+    else:
+        rows = self_loop_gpu_programs()
+        for name, value in SL_KNOBS[knob].items():
+            monkeypatch.setenv(name, value)
+        uf = int(SL_KNOBS[knob].get("MK_JIT_LOOP_UNROLL", 0)) or None
+    cases = _self_loop_cases(rows, uf)
+    assert len(check_cases(tmp_path, cases, machine=True)) == len(cases)  # none declined
+
+
+def emitted_loop_forms(src):
+    """[(form, uf, inc, T32's bound or None, inverted exit)] of the self-loops
+    in a machine lane's source, read off the text emit_self_loop writes."""
+    found = []
+    for case in re.split(r"\n    case \d+u: \{\n", src[src.index("MK_FN void mk_run"):])[1:]:
+        if "const uint32_t T = smax" not in case:
+            continue
+        uf = int(re.search(r"while \(more && T - it >= (\d+)u\)", case).group(1))
+        inc = int(re.search(r"const uint32_t T = .* / (\d+)u : 0u;", case).group(1))
+        t32 = re.search(r"const uint32_t T32 = T < (\d+)u", case)
+        inverted = re.search(r"L\.sb = \(a \|\| \(!", case) is not None
+        if "uint32_t k = 0u;" in case:  # the per-lane counter
+            assert "L.steps = s0 + %du * k;" % inc in case and t32 is None
+            found.append(("k", uf, inc, None, inverted))
+            continue
+        ind = re.search(r"const int64_t i0 = L\.r(\d+);", case).group(1)
+        assert t32
+        trip = "inverse" if re.search(r"L\.steps = s0 \+ \d+u \* \(\(uint32_t\)\(.* >> \d+\) \* \d+u\);", case) else "shift"
+        if trip == "shift":
+            assert re.search(r"L\.steps = s0 \+ \d+u \* \(uint32_t\)\(.* >> \d+\);", case)
+        phase = [name for name, mark in (("counter", "const uint32_t z0 = f0 ?"), ("satdown", "const int32_t f0 = MK_FLAG_GT(x), x0 = x;"),
+                                         ("mad24", "x = MK_MAD24(f, "), ("pm1", "(uint32_t)f);"),
+                                         ("narrow", "    int64_t n%s = (int64_t)x;\n" % ind)) if mark in case]
+        assert len(phase) == 1, (phase, case)
+        found.append((f"{phase[0]}/{trip}", uf, inc, int(t32.group(1)), inverted))
+    return found
+
+
+SL_FORMS = {"satdown/shift", "counter/shift", "counter/inverse", "pm1/shift", "mad24/shift", "mad24/inverse",
+            "narrow/shift", "narrow/inverse", "k"}
+
+
+def test_self_loop_forms_are_pinned():
+    # each row reaches the form its generator names; a change in
+    # emit_self_loop that moves a row to another form fails here
+    seen, t32_zero, polar = set(), 0, set()
+    for label, nodes, want in self_loop_programs():
+        loops = emitted_loop_forms(sc.jit_lane(nodes, machine=True)[0])
+        assert "+".join(sorted(f[0] for f in loops)) == want, (label, loops)
+        m = self_loop_meta(label)
+        assert len(loops) == m["nloops"] and (m["uf"], m["inc"]) in [(f[1], f[2]) for f in loops], (label, loops, m)
+        seen |= {f[0] for f in loops}
+        t32_zero += any(f[3] == 0 for f in loops)
+        polar |= {f[4] for f in loops}
+        if m["nloops"] == 1:
+            assert loops[0][4] == label.split("/")[2].startswith("i"), (label, loops)
+    assert seen == SL_FORMS, seen ^ SL_FORMS
+    assert t32_zero >= 12 and polar == {False, True}  # |step| > 2^30 - 1: the narrow phase entered for no iteration
+
+
+def test_self_loop_gpu_subset_covers_forms_and_steps():
+    rows, few = self_loop_gpu_programs(), self_loop_gpu_programs(few=True)
+    assert len(rows) == 48 and len(few) == 12 and {r[0] for r in few} <= {r[0] for r in rows}
+    assert {f for r in rows for f in r[2].split("+")} == SL_FORMS
+    single = [r[0].split("/") for r in rows if not r[0].startswith("chain/")]
+    assert {abs(int(s[1])) for s in single} == set(SELF_LOOP_STEPS)
+    assert {s[2] for s in single} == set(SELF_LOOP_EXITS)
+    assert {s[0] for s in single} == {"bump", "bak", "twice", "neg", "other", "addacc"}
+    assert {f.split("/")[0] for r in few for f in r[2].split("+")} >= {"satdown", "counter", "mad24", "narrow", "k"}
+
+
+def self_loop_endings(label, nodes, lanes=SL_LANES):
+    """Which ways the row's lanes end in its last loop over its inputs and
+    budgets, from the oracle alone: steps at the loop's entry from the row's
+    `head` program, iterations from the steps beyond them."""
+    m = self_loop_meta(label)
+    xs = np.asarray(self_loop_inputs(label, lanes), np.int64)
+    net = po.OracleNet(nodes)
+    entry = po.OracleNet([("n", "program", m["head"])]).compute_batch(xs)[2].astype(np.int64) - 1  # less its OUT
+    _, st, sp = net.compute_batch(xs, budget=6000)
+    done = (st & mk._native.MK_ST_REASON_MASK) != mk._native.MK_ST_BUDGET
+    tail = len(nodes[0][2].splitlines()) - len(m["head"].splitlines()) + 1 - m["inc"]  # lines behind the loop
+    trips = -(-(sp.astype(np.int64) - tail - entry) // m["inc"])
+    ends = set()
+    if (done & (trips >= 2 * m["uf"])).any():
+        ends.add("late")
+    if (done & (trips == 1)).any():
+        ends.add("first")   # the block ahead of the loop runs its first iteration: such a lane never enters it
+    if (done & (trips == 2)).any():
+        ends.add("second")  # ... and this one leaves at the first test the loop's own code makes
+
+    def cut_by(b):  # iterations completed by the lanes budget b stops inside the loop
+        _, stb, spb = net.compute_batch(xs, budget=b)
+        cut = ((stb & mk._native.MK_ST_REASON_MASK) == mk._native.MK_ST_BUDGET) & (spb > entry) & \
+            (~done | (spb < sp - tail))
+        return (spb.astype(np.int64) - entry)[cut] // m["inc"]
+
+    budgets = self_loop_budgets(label)
+    if any((cut_by(b) >= m["uf"]).any() for b in reversed(budgets)):
+        ends.add("budget-unguarded")  # behind one unguarded chunk or more
+    if any((cut_by(b) < m["uf"]).any() for b in budgets):
+        ends.add("budget-guarded")    # the budget leaves the loop no unguarded chunk
+    return ends
+
+
+def test_self_loop_cases_end_every_way():
+    # A row whose lanes all ended one way would pass the family test without
+    # running the rest of its loop's code.  Rows that cannot leave by the
+    # branch after 2 uf iterations, or at the first test, by name and reason;
+    # the other three ways are asked of them too.
+    reasons = {"JEZ": "stays only while the register is 0", "iJNZ": "stays only while the register is 0"}
+    cannot = {}
+    for label, _, _ in self_loop_programs():
+        m = self_loop_meta(label)
+        if m["late"] and m["first"]:
+            continue
+        body, step, exit_ = label.split("/")
+        cannot[label] = ({"first"}, "a != 0 loop leaves at its first test from x = step: 512 times the input is "
+                         "never an odd step") if m["late"] else \
+            ({"late", "budget-unguarded"} if body == "bump" and exit_ in reasons else  # two trips at the most
+             {"late", "second"},  # one trip or no end (2 x + s: it doubles away from 0)
+             "the exit test reads a register the body does not write" if body == "other" else
+             "2 x + s leaves 2^63 within 64 iterations" if body == "addacc" else
+             reasons.get(exit_, "the bump runs away from the exit test"))
+    assert len(cannot) * 5 <= len(self_loop_programs()), len(cannot)
+    for label, nodes, _ in self_loop_programs():
+        want = {"late", "first", "second", "budget-unguarded", "budget-guarded"} - cannot.get(label, (set(),))[0]
+        if "first" not in want:
+            want.discard("second")  # x = 2 step is as far from 512 times an input
+        ends = self_loop_endings(label, nodes)
+        assert want <= ends, (label, want - ends, cannot.get(label))
 
 
 # The countdown's saturating decrements in asm blocks of MK_JIT_SAT_BLOCK

@@ -11,10 +11,13 @@ Two generators:
 
 Further down: loop shapes of the native machine kernel, networks whose stack
 depths follow the data (``stack_loop_network``) and deep static stacks
-(``deep_stack_network``: spilled entries, shared and interfering slots).
+(``deep_stack_network``: spilled entries, shared and interfering slots); last,
+the self-loop family (``self_loop_programs``: steps, exit tests, bodies and
+chains around every form the native tier's loop generator can emit).
 """
 from __future__ import annotations
 
+import functools
 import random
 
 IMM_EDGES = [
@@ -585,3 +588,288 @@ def rotated_seed_kwargs(seed: int) -> dict:
     unguarded chunk) added."""
     kw = dict(budget=[None, 57, 300, 2000][seed % 4], stack_cap=[None, 3, 17, 33, 64, 200][seed % 6])
     return {k: v for k, v in kw.items() if v is not None}
+
+
+# ---- the self-loop family: steps, exit tests, bodies and chains ----------------
+# emit_self_loop (tis_jit.cpp) picks the form of a data-dependent loop from its
+# step, its exit test and its body.  Every row here names the form it is meant
+# to reach (test_jit_codegen.py test_self_loop_forms_are_pinned reads the form
+# back from the emitted lane):
+#
+#   "<phase>/<trip count>"   phase: satdown (step -1, JGZ: saturating countdown),
+#       counter (JGZ with step <= -2, JLZ with step >= 1: z0 = ceil(|x1| / k)),
+#       pm1 / mad24 (int-flag loop, the bump x +- f or MK_MAD24), narrow (the
+#       generic 32-bit phase); trip count: shift (the step a power of two) or
+#       inverse (a multiply by the inverse of its odd part)
+#   "k"                      no induction register: the per-lane counter
+#
+# a chain's form is its loops' forms, sorted, joined by "+".
+SELF_LOOP_STEPS = (1, 2, 3, 5, 6, 12, 48, 255, 8388607, 8388608, 8388609, 1073741823, 1073741824, 1073741825,
+                   2147483647, 2147483648, 4294967296)
+# "JGZ": `Jcc L` at the loop's bottom; "iJGZ": `Jcc E / JMP L / E:`
+SELF_LOOP_EXITS = ("JGZ", "JLZ", "JNZ", "JEZ", "iJGZ", "iJLZ", "iJNZ", "iJEZ")
+# the sign of the bump under which the exit test can end a long loop ("" never:
+# the loop stays only while the register is 0)
+_ENDS = {"JGZ": "-", "iJLZ": "-", "JLZ": "+", "iJGZ": "+", "JNZ": "+-", "iJEZ": "+-", "JEZ": "", "iJNZ": ""}
+SELF_LOOP_BODIES = ("bump", "bak", "twice", "neg", "other", "addacc")
+# unguarded iterations per exit test (tis_jit.cpp fast_unroll of the body's
+# micro-ops; SWP is a renaming, NEG and ADD ACC are not bumps)
+_BODY_UF = {"bump": 32, "bak": 32, "twice": 32, "neg": 16, "other": 32, "addacc": 16}
+_BIG = 2**30 - 1   # from this step on the input is scaled by 512 ahead of the loop: 64 trips need |x| > 2^31
+_SCALE = 9         # `ADD ACC` lines of that prelude
+# steps of the rows that cannot leave by the branch late (below): a sample, not the product
+_FEW = (1, 255, 8388607, 1073741824)
+
+
+def _body_lines(body: str, s: int) -> list:
+    """The loop body for the signed step ``s``."""
+    bump = f"ADD {s}" if s > 0 else f"SUB {-s}"
+    back = f"SUB {s}" if s > 0 else f"ADD {-s}"
+    return {
+        "bump": [bump],
+        "bak": [bump, "SWP", "ADD 3", "SWP"],        # work on BAK beside the counter: the generic narrow phase
+        "twice": [bump, bump],                       # the register written twice: no induction register
+        "neg": ["NEG", back, "NEG"],                 # -(-x - s) = x + s
+        "other": ["SWP", bump, "SWP"],               # the counter in BAK, the exit test on ACC
+        "addacc": ["ADD ACC", bump],                 # 2 x + s: no constant bump at all
+    }[body]
+
+
+def _loop_lines(lab: str, body: list, exit_: str) -> list:
+    """One loop; a line that starts with ':' carries the label of whatever follows."""
+    lines = [f"{lab}: {body[0]}"] + body[1:]
+    if exit_.startswith("i"):
+        return lines + [f"{exit_[1:]} E{lab}", f"JMP {lab}", f":E{lab}"]
+    return lines + [f"{exit_} {lab}"]
+
+
+def _join(lines: list) -> str:
+    out, pend = [], ""
+    for ln in lines:
+        if ln.startswith(":"):
+            pend = ln[1:] + ": "
+        else:
+            out.append(pend + ln)
+            pend = ""
+    assert not pend
+    return "\n".join(out)
+
+
+def _loop_form(body: str, s: int, exit_: str) -> str:
+    """The form emit_self_loop is meant to pick (the rules of int_flag_fn and
+    of the induction register, restated)."""
+    ad = abs(s)
+    if body in ("twice", "neg", "addacc"):
+        return "k"
+    if ad >= 2**31:  # no induction register on the counter; `bak` still has BAK's += 3
+        return "narrow/inverse" if body == "bak" else "k"
+    trip = "shift" if ad & (ad - 1) == 0 else "inverse"
+    flag = {"JGZ": "GT", "JLZ": "LT", "JNZ": "NZ", "iJEZ": "NZ"}.get(exit_)
+    if body != "bump" or ad >= 2**23 or flag is None:
+        return f"narrow/{trip}"
+    if s == -1 and flag == "GT":
+        return f"satdown/{trip}"
+    if (flag == "GT" and s <= -2) or (flag == "LT" and s >= 1):
+        return f"counter/{trip}"
+    return f"{'pm1' if ad == 1 else 'mad24'}/{trip}"
+
+
+def _single(body: str, s: int, exit_: str):
+    big = abs(s) >= _BIG
+    pre = ["IN ACC"] + ["ADD ACC"] * (_SCALE if big else 0) + (["SAV"] if body in ("bak", "other") else [])
+    blines = _body_lines(body, s)
+    tail = {"bak": ["MOV ACC, n:R0", "SWP", "ADD R0", "OUT ACC"], "other": ["SWP", "OUT ACC"]}.get(body, ["OUT ACC"])
+    label = f"{body}/{'+' if s > 0 else '-'}{abs(s)}/{exit_}"
+    eff = 2 * s if body == "twice" else s
+    meta = dict(uf=_BODY_UF[body], inc=len(blines) + (2 if exit_.startswith("i") else 1), prelude=len(pre),
+                mult=2**_SCALE if big else 1, step=eff, head=_join(pre + ["OUT ACC"]),
+                late=("+" if s > 0 else "-") in _ENDS[exit_] and body not in ("other", "addacc"),
+                # leaving at the first test of a != 0 loop takes x = the step: 512 times the input is never an odd one
+                first=not (big and eff % 2**_SCALE and exit_ in ("JNZ", "iJEZ")), nloops=1)
+    text = _join(pre + _loop_lines("L", blines, exit_) + tail)
+    return label, [("n", "program", text)], _loop_form(body, s, exit_), meta
+
+
+def _chains():
+    """A prelude whose step count follows the input (6, 8 or 9 steps), then
+    two or three loops of different forms: the lanes of a wave reach the later
+    loops with different step counts, and the unguarded iterations T follow
+    the wave's largest.  The last loop is the one the budgets are aimed at."""
+    pre = ["IN ACC", "SAV", "JGZ P", "NOP", "NOP", "NOP", ":P", "JLZ Q", "NOP", ":Q", "NOP"]
+    rows = []
+
+    def chain(name, loops, step):
+        # loops: [(lines between the loops, body, step, exit)]
+        lines, forms = list(pre), []
+        for k, (between, body, s, exit_) in enumerate(loops):
+            lines += between
+            if k == len(loops) - 1:
+                head = _join(lines + ["OUT ACC"])
+            lines += _loop_lines(f"L{k}", _body_lines(body, s), exit_)
+            forms.append(_loop_form(body, s, exit_))
+        body, s, exit_ = loops[-1][1:]
+        meta = dict(uf=_BODY_UF[body], inc=len(_body_lines(body, s)) + (2 if exit_.startswith("i") else 1),
+                    prelude=6, mult=1, step=step, head=head, late=True, first=True, nloops=len(loops))
+        rows.append((f"chain/{name}", [("n", "program", _join(lines + ["OUT ACC"]))], "+".join(sorted(forms)), meta))
+
+    again = ["SWP", "SAV"]  # ACC = the input again (BAK keeps it)
+    chain("down1-up6-nz7", [([], "bump", -1, "JGZ"), (again, "bump", 6, "JLZ"), (again, "bump", -7, "JNZ")], 7)
+    chain("up1-down3", [([], "bump", 1, "JLZ"), (again, "bump", -3, "JGZ")], 3)
+    chain("nz1-bak5", [([], "bump", -1, "JNZ"), (again, "bak", -5, "JGZ")], 5)
+    chain("twice2-inv12", [([], "twice", -2, "JGZ"), (again, "bump", 12, "iJGZ")], 12)
+    chain("down1-const-down2", [([], "bump", -1, "JGZ"), (["MOV 100, ACC"], "bump", -2, "JGZ"),
+                                (again, "bump", -1, "iJLZ")], 1)
+    chain("down255-neg48", [([], "bump", -255, "JGZ"), (again, "neg", 48, "JLZ")], 48)
+    chain("wide-down1", [([], "bump", 2**30 + 1, "JLZ"), (again, "bump", -1, "JGZ")], 1)
+    chain("k-narrow", [([], "addacc", -5, "JGZ"), (again, "bump", -8388608, "JGZ")], 8388608)
+    return rows
+
+
+@functools.lru_cache(maxsize=None)
+def _self_loop_table():
+    rows = []
+    for body in ("bump", "bak", "twice", "neg"):  # the product: every step, both signs, every exit that can end it
+        for step in SELF_LOOP_STEPS:
+            for s in (step, -step):
+                for exit_ in SELF_LOOP_EXITS:
+                    if ("+" if s > 0 else "-") in _ENDS[exit_]:
+                        rows.append(_single(body, s, exit_))
+    # Rows that leave at the first test or never (the bump runs away from the
+    # exit test, or the loop stays only while the register is 0), the test on
+    # a register the body does not write, and 2 x + s: a sample of the steps.
+    # With MK_JIT_SAT_COUNT on these are the only MAD24 loops under the > 0
+    # and < 0 flags.
+    for step in _FEW:
+        for s in (step, -step):
+            for exit_ in SELF_LOOP_EXITS:
+                if ("+" if s > 0 else "-") not in _ENDS[exit_]:
+                    rows.append(_single("bump", s, exit_))
+    for step in (1, 8388609, 2147483648):
+        for s in (step, -step):
+            for exit_ in ("JGZ", "JLZ", "iJEZ", "iJNZ"):
+                rows.append(_single("other", s, exit_))
+    for s in (-5, 5, -255, 1073741825):
+        for exit_ in ("JGZ", "JLZ", "iJLZ", "iJGZ"):
+            rows.append(_single("addacc", s, exit_))
+    rows += _chains()
+    assert len({r[0] for r in rows}) == len(rows)
+    return {r[0]: r for r in rows}
+
+
+def self_loop_programs():
+    """[(label, nodes, expected_form)]: single loops '<body>/<signed step>/<exit>'
+    and chains 'chain/<name>'.
+
+    The product of SELF_LOOP_STEPS, both signs and SELF_LOOP_EXITS is taken
+    where the bump moves towards the exit (JNZ and the inverted JEZ: both
+    signs), over the bodies whose loops can then run long (bump, bak, twice,
+    neg).  The other half of the plain product -- a bump that runs away from
+    its exit test, and JEZ / inverted JNZ, which stay only while the register
+    is 0 -- leaves at the first test or never: of those, and of the `other`
+    and `addacc` bodies, a sample of steps is kept (under a fifth of the
+    rows, test_self_loop_cases_end_every_way lists them)."""
+    return [r[:3] for r in _self_loop_table().values()]
+
+
+def self_loop_meta(label: str) -> dict:
+    """What the tests need to know of a row: uf and inc (unguarded iterations
+    per exit test, steps per iteration) of its last loop, the static steps
+    ahead of the first loop, the factor between an input and the register at
+    the loop, and `head`: the program up to the last loop, then OUT ACC."""
+    return dict(_self_loop_table()[label][3])
+
+
+def _i32(v: int) -> int:
+    return max(-(2**31), min(2**31 - 1, v))
+
+
+def self_loop_inputs(label: str, n: int):
+    """Seeded by the label.  Multiples of the step up to 110 trips on both
+    sides of 0 (JNZ loops end only on those), values between, the edges of
+    _edge_inputs -- scaled down as well where the program scales its input up,
+    so that the loop sees +-2^30 -- and small values.  With a budget of 6,000
+    no lane walks further than that."""
+    import zlib
+
+    m = self_loop_meta(label)
+    rng = random.Random(zlib.crc32(label.encode()))
+    mult, ad = m["mult"], abs(m["step"])
+    span = 110
+    hi = _i32(span * ad // mult)
+    edges = [0, 1, -1, 2**30, -(2**30), 2**30 + 1, -(2**30) - 1, 2**31 - 1, -(2**31), 2**31 - 2, -(2**31) + 1]
+    if mult > 1:
+        edges += [2**30 // mult, -(2**30 // mult), 2**30 // mult + 1, -(2**30 // mult) - 1]
+
+    import math
+
+    q = mult // math.gcd(ad, mult)  # k * step is `mult` times an input for every q-th k
+
+    def multiple(k):
+        """The input for k trips to 0, or the nearest count an int32 input can give."""
+        sign = -1 if k < 0 else 1
+        k = max(q, (abs(k) + q // 2) // q * q)
+        while k and not -(2**31) <= sign * k * ad // mult < 2**31:
+            k -= q
+        return sign * k * ad // mult
+
+    # one and two trips (exactly to 0, and past it), just past two chunks of 32 and the longest, on both
+    # sides, and 0; then the seeded mix
+    half = [_i32(sign * k * ad // (2 * mult)) for k in (1, 3) for sign in (1, -1)]  # between the multiples
+    xs = ([multiple(k) for k in (1, -1, 2, -2, 70, -70, span, -span)] + [0] + half + [3, -3, 4, -4])[:n]
+    while len(xs) < n:
+        c = rng.random()
+        if c < 0.15:
+            xs.append(rng.choice(edges))
+        elif c < 0.25:
+            xs.append(rng.randint(-3, 3))
+        elif c < 0.65:
+            xs.append(multiple(rng.randint(-span, span)))
+        else:
+            xs.append(rng.randint(-hi, hi))
+    return xs
+
+
+def self_loop_budgets(label: str, uf: int | None = None) -> list:
+    """Every budget from 1 to prelude + 2 uf inc + inc + 8: the unguarded
+    iterations T of the loop pass 0, uf - 1, uf, uf + 1, 2 uf - 1, 2 uf and
+    2 uf + 1, at every position inside an iteration; then 997 and 6000.
+    ``uf``: another chunk size than the default (MK_JIT_LOOP_UNROLL).
+    Chains: up to 400, which walks the later loops' T for the step counts
+    their lanes arrive with."""
+    m = self_loop_meta(label)
+    top = m["prelude"] + 2 * (uf or m["uf"]) * m["inc"] + m["inc"] + 8
+    if m["nloops"] > 1:
+        top = max(top, 400)
+    return list(range(1, top + 1)) + [997, 6000]
+
+
+def _pick(rows, want):
+    """Rows by label, in the order asked."""
+    have = {r[0]: r for r in rows}
+    return [have[w] for w in want]
+
+
+# The GPU's subset: every form and every step at least once (both checked by
+# test_jit_codegen.py test_self_loop_gpu_subset_covers_forms_and_steps).
+SELF_LOOP_GPU = (
+    "bump/-1/JGZ", "bump/+1/JLZ", "bump/-2/JNZ", "bump/+3/JLZ", "bump/-5/JNZ", "bump/+6/iJEZ", "bump/-12/iJLZ",
+    "bump/+48/iJGZ", "bump/-255/JGZ", "bump/+255/JNZ", "bump/-8388607/JGZ", "bump/+8388607/iJEZ",
+    "bump/-8388607/JNZ", "bump/+8388608/JLZ", "bump/-8388608/JNZ", "bump/+8388609/iJEZ", "bump/-1073741823/JGZ",
+    "bump/+1073741824/JLZ", "bump/-1073741824/iJLZ", "bump/+1073741825/JNZ", "bump/-2147483647/JGZ",
+    "bump/+2147483647/iJGZ", "bump/-2147483648/JGZ", "bump/+4294967296/JLZ", "bump/+1/JNZ", "bump/-1/iJEZ",
+    "bump/+255/JGZ", "bump/-255/JLZ", "bump/+8388607/JGZ", "bump/-1/JEZ", "bump/+255/iJNZ", "bump/+1/JGZ",
+    "bak/-5/JGZ", "bak/+1/JLZ", "bak/-4294967296/JGZ", "bak/+1073741825/iJGZ", "twice/-3/JGZ", "twice/+2/JNZ",
+    "neg/-48/JGZ", "neg/+6/iJEZ", "other/-8388609/JGZ", "other/+1/iJEZ", "addacc/-5/JGZ",
+    "chain/down1-up6-nz7", "chain/up1-down3", "chain/nz1-bak5", "chain/down1-const-down2", "chain/wide-down1",
+)
+# ... and of those, the rows every machine variant and knob runs
+SELF_LOOP_GPU_FEW = (
+    "bump/-1/JGZ", "bump/+3/JLZ", "bump/-255/JGZ", "bump/-8388607/JNZ", "bump/+8388608/JLZ", "bump/-12/iJLZ",
+    "bump/+255/JGZ", "bump/-1073741823/JGZ", "bump/+4294967296/JLZ", "bak/-5/JGZ", "neg/-48/JGZ",
+    "chain/down1-up6-nz7",
+)
+
+
+def self_loop_gpu_programs(few: bool = False):
+    """The curated rows of self_loop_programs for the GPU (48; few: 12)."""
+    return _pick(self_loop_programs(), SELF_LOOP_GPU_FEW if few else SELF_LOOP_GPU)
