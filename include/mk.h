@@ -329,6 +329,61 @@ int mk_session_reset_indexed(mk_session *s, const uint32_t *sel, size_t m);
  * session.  Synchronous. */
 int mk_session_call_open(mk_session *s, const uint32_t *sel, size_t m, uint8_t *open);
 
+/* ---- open calls: the list, the device resume and the drain -------------------
+ * A call that outlives its budget slice stays open (MK_ST_BUDGET) until
+ * resumes finish it.  These forms find and finish open calls on the GPU.
+ * sel[0..m) as in the indexed forms; sel NULL with m == n: every session.  The
+ * host forms check the list and return MK_EINVAL before anything is queued; the
+ * device forms take it ON TRUST under the contract of
+ * mk_session_compute_indexed_device, and an entry >= n touches nothing.
+ * m == 0 is MK_OK and launches nothing.  All of them are ordered against every
+ * other launch of the set like the indexed forms.  Their scratch belongs to the
+ * set and grows on demand: a call synchronises only when it has to grow (it
+ * never shrinks), and MK_ENOMEM leaves the set usable.
+ *
+ * The open list: list[0..*count) holds the listed sessions that have a call
+ * open (what mk_session_call_open reports), in increasing order, and pos[k]
+ * (nullable) the t with sel[t] == list[k] -- list[k] itself for a null sel.
+ * list[*count..m) is 0xffffffff and pos[*count..m) is 0, the padding of
+ * mk_requests_group_device: the list is a valid d_sel of the indexed and ragged
+ * device forms over m entries with no read-back of the count.  list and pos
+ * have m words and must not overlap sel. */
+int mk_session_open_list(mk_session *s, const uint32_t *sel, size_t m, uint32_t *list, uint32_t *pos /* nullable */,
+                         size_t *count);
+/* Device form, asynchronous on `stream`; *d_count is one word. */
+int mk_session_open_list_device(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t *d_list,
+                                uint32_t *d_pos /* nullable */, uint32_t *d_count, void *stream);
+/* mk_session_step_indexed(in = NULL) on device arrays of m columns,
+ * asynchronous on `stream`: one more budget slice of the listed sessions' open
+ * calls.  A listed session without one reports out 0, steps 0 and status 0, or
+ * MK_ST_STACK_OVERFLOW if it has ended, as the host form does. */
+int mk_session_resume_device(mk_session *s, const uint32_t *d_sel, size_t m, int32_t *d_out, uint8_t *d_status,
+                             uint32_t *d_steps /* nullable */, void *stream);
+/* The drain: resumes the listed sessions' open calls slice after slice until
+ * they answer or max_slices slices have run.  Its result is that of
+ *   slice 1                mk_session_step_indexed(sel, in = NULL)
+ *   slices 2..max_slices   the same on exactly the entries whose last status
+ *                          was MK_ST_BUDGET
+ * with entry t reporting, at column t of m, the out, status and steps of the
+ * last slice that ran it (steps accumulate over a call's slices, as a resume
+ * reports them); an entry with no call open at the start reports what
+ * mk_session_resume_device does.  *still_open (nullable) is the number of
+ * entries whose final status is MK_ST_BUDGET; MK_OK whether or not calls stay
+ * open.  On the GPU the open calls are packed into a list (above) and each
+ * slice runs over the list alone, repacked after it, so a slice costs what the
+ * calls still open cost, not the whole set.  MK_EINVAL for max_slices == 0 and
+ * for sets of a network with remote peers: there the host serves the peers
+ * between slices.  The host form is synchronous and stops at the first slice
+ * that leaves nothing open. */
+int mk_session_drain(mk_session *s, const uint32_t *sel, size_t m, uint32_t max_slices, int32_t *out,
+                     uint8_t *status, uint32_t *steps /* nullable */, size_t *still_open /* nullable */);
+/* Device form, asynchronous on `stream` and without any read-back: all
+ * max_slices slices are queued over m entries, those past the last open call
+ * over padding that the `>= n` guard drops.  *d_still_open is one word. */
+int mk_session_drain_device(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t max_slices, int32_t *d_out,
+                            uint8_t *d_status, uint32_t *d_steps /* nullable */,
+                            uint32_t *d_still_open /* nullable */, void *stream);
+
 /* ---- ragged bursts: each listed session its own number of calls -------------
  * sel[0..m) as in the indexed forms; sel NULL with m == n: every session.
  * off[0..m] (uint32_t) gives each entry's place in the I/O arrays: off[0] == 0,

@@ -458,6 +458,55 @@ func (s *Sessions) CallOpen(sel []uint32) ([]bool, error) {
 	return open, nil
 }
 
+// OpenList returns the listed instances that have a call open (sel nil: all
+// n), found and packed on the GPU, in increasing order -- itself a valid list
+// for the indexed forms -- and for each its position in sel (the instance
+// itself for a nil sel) -- mk_session_open_list.
+func (s *Sessions) OpenList(sel []uint32) (list, pos []uint32, err error) {
+	m := len(sel)
+	if sel == nil {
+		m = s.n
+	}
+	if m == 0 {
+		return nil, nil, nil
+	}
+	list, pos = make([]uint32, m), make([]uint32, m)
+	var cnt C.size_t
+	rc := C.mk_session_open_list(s.s, selPtr(sel), C.size_t(m), (*C.uint32_t)(unsafe.Pointer(&list[0])),
+		(*C.uint32_t)(unsafe.Pointer(&pos[0])), &cnt)
+	if rc != C.MK_OK {
+		return nil, nil, fmt.Errorf("mk_session_open_list: %d", int(rc))
+	}
+	return list[:int(cnt)], pos[:int(cnt)], nil
+}
+
+// Drain finishes the listed instances' open calls (sel nil: all n): a resume
+// of them, then of those still out of budget, up to maxSlices times, every
+// slice over a packed list of the calls still open.  Entry t of the result is
+// the last slice that ran instance sel[t]; one without an open call reports
+// what a resume does.  stillOpen counts the calls left open at the limit
+// (mk_session_drain).
+func (s *Sessions) Drain(sel []uint32, maxSlices uint32) (r *Result, stillOpen int, err error) {
+	m := len(sel)
+	if sel == nil {
+		m = s.n
+	}
+	if maxSlices == 0 {
+		return nil, 0, fmt.Errorf("mk: a drain takes at least one slice")
+	}
+	if m == 0 {
+		return &Result{}, 0, nil
+	}
+	r = &Result{Out: make([]int32, m), Status: make([]uint8, m), Steps: make([]uint32, m)}
+	var left C.size_t
+	rc := C.mk_session_drain(s.s, selPtr(sel), C.size_t(m), C.uint32_t(maxSlices), (*C.int32_t)(unsafe.Pointer(&r.Out[0])),
+		(*C.uint8_t)(unsafe.Pointer(&r.Status[0])), (*C.uint32_t)(unsafe.Pointer(&r.Steps[0])), &left)
+	if rc != C.MK_OK {
+		return nil, 0, fmt.Errorf("mk_session_drain: %d", int(rc))
+	}
+	return r, int(left), nil
+}
+
 // Promote hands the listed instances that the interpreter holds between calls
 // back to the native tier (sel nil: all n) and reports, in list order, which
 // were promoted -- mk_session_promote.  An instance with a call open, one the

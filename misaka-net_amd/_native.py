@@ -140,6 +140,18 @@ SIGNATURES = {
     "mk_session_cancel_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mk_session_reset_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mk_session_call_open": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mk_session_open_list": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "mk_session_open_list_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_resume_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_drain": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.POINTER(C.c_size_t)]),
+    "mk_session_drain_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p]),
     "mk_session_compute_ragged": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mk_session_compute_ragged_device": (

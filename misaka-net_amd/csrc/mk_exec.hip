@@ -3089,6 +3089,8 @@ void *pick_session_kernel(int nprog, bool sel = false)
 } // namespace
 } // namespace mk
 
+#include "sess_drain.h"
+
 struct mk_session {
     mk_net *h = nullptr;
     int device = 0;
@@ -3106,6 +3108,13 @@ struct mk_session {
     // for queue_cap requests, grown on demand
     void *d_queue = nullptr;
     size_t queue_cap = 0;
+    // open lists and drains (sess_drain.h): two lists with their caller
+    // columns, the compact I/O of a resume slice, the scan's words and the
+    // count, one allocation with room for drain_cap entries, grown on demand;
+    // h_drain: the pinned word the host drain reads the count into
+    void *d_drain = nullptr;
+    size_t drain_cap = 0;
+    uint32_t *h_drain = nullptr;
     hipStream_t stream = nullptr;
     mk::SessParams p{};
     // native tier (tis_jit.h mk_sess_exec): the session schedule compiled to
@@ -3166,6 +3175,8 @@ struct mk_session {
         (void)hipFree(d_stage);
         (void)hipHostFree(h_stage);
         (void)hipFree(d_queue);
+        (void)hipFree(d_drain);
+        (void)hipHostFree(h_drain);
         mk::release_module(mod);
         if (order) (void)hipEventDestroy(order);
         if (stream) (void)hipStreamDestroy(stream);
@@ -3734,6 +3745,134 @@ int queue_launch(mk_session *s, const uint32_t *d_ids, const int64_t *d_in, size
         if (hipGetLastError() != hipSuccess) rc = MK_EDEVICE;
     }
     // the scatter is the launch's last kernel: later work on another stream waits for it
+    if (queued) {
+        const int mr = session_mark(s, st);
+        if (rc == MK_OK) rc = mr;
+    }
+    return rc;
+}
+
+// The drain scratch of a set, for lists of `cap` entries (sess_drain.h).
+struct DrainBufs {
+    uint32_t *list[2], *pos[2]; // the list a slice runs over and the one its fold packs
+    int32_t *out;               // a slice's compact columns
+    uint32_t *steps;
+    uint8_t *status;
+    uint32_t *words, *sums, *count;
+    // the inputs of a device resume: the kernel loads a listed session's word
+    // when it has no call to continue (and ignores it).  Zero since allocation.
+    const int64_t *in;
+    size_t bytes;
+};
+
+DrainBufs drain_layout(size_t cap, void *base)
+{
+    Carver k(base);
+    DrainBufs d{};
+    for (int b = 0; b < 2; b++) {
+        d.list[b] = k.take<uint32_t>(cap);
+        d.pos[b] = k.take<uint32_t>(cap);
+    }
+    d.out = k.take<int32_t>(cap);
+    d.steps = k.take<uint32_t>(cap);
+    d.status = k.take<uint8_t>(cap);
+    d.words = k.take<uint32_t>(cap);
+    d.sums = k.take<uint32_t>(rg::rg_scan_blocks(cap));
+    d.count = k.take<uint32_t>(1);
+    d.in = k.take<int64_t>(cap);
+    d.bytes = k.at;
+    return d;
+}
+
+// Room for lists of m <= n entries, as queue_reserve: growing waits for the
+// set's last launch, a failed allocation leaves the set without a scratch and
+// usable.  Caller holds s->mu and has the device current.
+int drain_reserve(mk_session *s, size_t m)
+{
+    if (!s->h_drain && hipHostMalloc((void **)&s->h_drain, 8, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        s->h_drain = nullptr;
+        return MK_ENOMEM;
+    }
+    if (m <= s->drain_cap) return MK_OK;
+    if (s->last && s->order && hipEventSynchronize(s->order) != hipSuccess) return MK_EDEVICE;
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
+    (void)hipFree(s->d_drain);
+    s->d_drain = nullptr;
+    s->drain_cap = 0;
+    const size_t cap = std::min<size_t>(std::max<size_t>(m + m / 2, 4096), std::max<size_t>(s->n, m));
+    if (hipMalloc(&s->d_drain, drain_layout(cap, nullptr).bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        s->d_drain = nullptr;
+        return MK_ENOMEM;
+    }
+    const DrainBufs d = drain_layout(cap, s->d_drain);
+    if (hipMemset((void *)d.in, 0, cap * 8) != hipSuccess) {
+        (void)hipFree(s->d_drain);
+        s->d_drain = nullptr;
+        return MK_EDEVICE;
+    }
+    s->drain_cap = cap;
+    return MK_OK;
+}
+
+// The open calls among the m listed sessions into d_list / d_pos (nullable) /
+// d_count on `st`.  Caller holds s->mu, has the device current, has ordered
+// `st` after the set's last launch and marks it; 1 <= m <= n < 2^32.
+int open_list_launch(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t *d_list, uint32_t *d_pos,
+                     uint32_t *d_count, hipStream_t st)
+{
+    if (s->broken) return MK_EDEVICE;
+    if (int rc = drain_reserve(s, m)) return rc;
+    const DrainBufs d = drain_layout(s->drain_cap, s->d_drain);
+    const dr::DrOpen src{s->p.io, s->p.nsb, (uint32_t)s->n, d_sel, nullptr, nullptr, nullptr};
+    return dr::dr_compact(src, (uint32_t)m, d_list, d_pos, d_count, nullptr, d.words, d.sums, st);
+}
+
+// The drain on `st` into the caller's device columns: the entry pass (every
+// column its answer without an open call, the open ones into the first list),
+// then slice after slice a resume over the current list into the compact
+// columns and the fold that returns them and packs the next list.  `left`
+// null: the device form, every slice over m entries, the count never read.
+// Otherwise the host form (st is s->stream): the count read back after every
+// fold, the next slice over that many entries, none at 0; *left takes the
+// last.  Caller as for queue_launch; 1 <= m <= n < 2^32, max_slices >= 1.
+int drain_launch(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t max_slices, int32_t *d_out,
+                 uint8_t *d_status, uint32_t *d_steps, uint32_t *d_still, size_t *left, hipStream_t st)
+{
+    if (s->broken) return MK_EDEVICE;
+    if (int rc = drain_reserve(s, m)) return rc;
+    const DrainBufs d = drain_layout(s->drain_cap, s->d_drain);
+    const uint32_t n = (uint32_t)s->n;
+    // whatever gets queued reads and writes the scratch: a later launch that grows it must wait
+    bool queued = true;
+    auto count = [&](uint32_t *len) {
+        if (hipMemcpyAsync(s->h_drain, d.count, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return (int)MK_EDEVICE;
+        *len = std::min(*len, s->h_drain[0]);
+        return (int)MK_OK;
+    };
+    const dr::DrOpen entry{s->p.io, s->p.nsb, n, d_sel, d_out, d_status, d_steps};
+    int rc = dr::dr_compact(entry, (uint32_t)m, d.list[0], d.pos[0], d.count, d_still, d.words, d.sums, st);
+    uint32_t len = (uint32_t)m;
+    int cur = 0;
+    for (uint32_t k = 0; rc == MK_OK && k < max_slices; k++) {
+        if (left && ((rc = count(&len)) != MK_OK || len == 0)) break;
+        SessCall c = SessCall::io(d.in, d.out, d.status, d_steps ? d.steps : nullptr);
+        c.resume = true;
+        c.sel = d.list[cur];
+        c.m = len;
+        if ((rc = session_launch(s, c, st, &queued)) != MK_OK) break;
+        const dr::DrFold fold{d.list[cur], d.pos[cur], n, d.out, d.status, d_steps ? d.steps : nullptr, d_out,
+                              d_status, d_steps};
+        rc = dr::dr_compact(fold, len, d.list[cur ^ 1], d.pos[cur ^ 1], d.count, d_still, d.words, d.sums, st);
+        cur ^= 1;
+    }
+    if (rc == MK_OK && left) {
+        if (len) rc = count(&len);
+        *left = len;
+    }
     if (queued) {
         const int mr = session_mark(s, st);
         if (rc == MK_OK) rc = mr;
@@ -4575,6 +4714,106 @@ int mk_session_call_open(mk_session *s, const uint32_t *sel, size_t m, uint8_t *
         return MK_EDEVICE;
     memcpy(open, (char *)s->h_stage + o_open, m);
     return MK_OK;
+}
+
+// ---- open calls: the list, the device resume and the drain (sess_drain.h) -----
+int mk_session_open_list(mk_session *s, const uint32_t *sel, size_t m, uint32_t *list, uint32_t *pos, size_t *count)
+{
+    if (!s || !count || (m && !list)) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (sel ? !mk::sel_valid(s, sel, m) : m != s->n) return MK_EINVAL; // a null list: every session, m == n
+    *count = 0;
+    if (m == 0) return MK_OK;
+    if (s->n > 0xffffffffull) return MK_ELIMIT;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    uint32_t *d_sel;
+    const size_t col = mk::Carver::al(m * 4);
+    size_t o = 2 * col + 256; // list, pos and the count behind the staged list
+    if (int rc = mk::session_stage_sel(s, sel, m, &o, &d_sel)) return rc;
+    char *b = (char *)s->d_stage + o, *hb = (char *)s->h_stage + o;
+    if (int rc = mk::open_list_launch(s, d_sel, m, (uint32_t *)b, (uint32_t *)(b + col), (uint32_t *)(b + 2 * col),
+                                      s->stream))
+        return rc;
+    if (hipMemcpyAsync(hb, b, 2 * col + 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipStreamSynchronize(s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    memcpy(list, hb, m * 4);
+    if (pos) memcpy(pos, hb + col, m * 4);
+    *count = *(const uint32_t *)(hb + 2 * col);
+    return MK_OK;
+}
+
+int mk_session_open_list_device(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t *d_list, uint32_t *d_pos,
+                                uint32_t *d_count, void *stream)
+{
+    if (!s || (m && (!d_list || !d_count))) return MK_EINVAL;
+    if (m > s->n || (!d_sel && m != s->n)) return MK_EINVAL;
+    if (m == 0) return MK_OK;
+    if (s->n > 0xffffffffull) return MK_ELIMIT;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::DeviceGuard g(s->device);
+    hipStream_t st;
+    if (int rc = mk::session_enter(s, stream, &st)) return rc;
+    int rc = mk::open_list_launch(s, d_sel, m, d_list, d_pos, d_count, st);
+    // it read the set's state: a later launch on another stream waits for it
+    const int mr = mk::session_mark(s, st);
+    return rc ? rc : mr;
+}
+
+int mk_session_resume_device(mk_session *s, const uint32_t *d_sel, size_t m, int32_t *d_out, uint8_t *d_status,
+                             uint32_t *d_steps, void *stream)
+{
+    if (!s || (m && (!d_out || !d_status))) return MK_EINVAL;
+    if (m > s->n || (!d_sel && m != s->n)) return MK_EINVAL;
+    if (m == 0) return MK_OK;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::drain_reserve(s, m)) return rc; // for its zero inputs
+    mk::SessCall k = mk::SessCall::io(mk::drain_layout(s->drain_cap, s->d_drain).in, d_out, d_status, d_steps);
+    k.resume = true;
+    k.sel = d_sel; // null: the plain launch on all n
+    k.m = m;
+    return mk::session_on_stream(s, stream, [&](hipStream_t st, bool *queued, hipEvent_t done) {
+        return mk::session_launch(s, k, st, queued, done);
+    });
+}
+
+int mk_session_drain(mk_session *s, const uint32_t *sel, size_t m, uint32_t max_slices, int32_t *out,
+                     uint8_t *status, uint32_t *steps, size_t *still_open)
+{
+    if (!s || max_slices == 0 || (m && (!out || !status))) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->p.mixed) return MK_EINVAL; // the host serves the peers between slices: not a drain
+    if (sel ? !mk::sel_valid(s, sel, m) : m != s->n) return MK_EINVAL;
+    if (still_open) *still_open = 0;
+    if (m == 0) return MK_OK;
+    if (s->n > 0xffffffffull) return MK_ELIMIT;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    size_t left = 0;
+    mk::HostIO io = mk::HostIO::of(m, nullptr, out, status, steps);
+    io.m = m;
+    io.sel = sel;
+    int rc = mk::session_round_trip(s, io, [&](const mk::StageDev &d) {
+        return mk::drain_launch(s, d.sel, m, max_slices, d.out, d.status, d.steps, nullptr, &left, s->stream);
+    });
+    if (rc == MK_OK && still_open) *still_open = left;
+    return rc;
+}
+
+int mk_session_drain_device(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t max_slices, int32_t *d_out,
+                            uint8_t *d_status, uint32_t *d_steps, uint32_t *d_still_open, void *stream)
+{
+    if (!s || max_slices == 0 || (m && (!d_out || !d_status))) return MK_EINVAL;
+    if (s->p.mixed || m > s->n || (!d_sel && m != s->n)) return MK_EINVAL;
+    if (m == 0) return MK_OK;
+    if (s->n > 0xffffffffull) return MK_ELIMIT;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::DeviceGuard g(s->device);
+    hipStream_t st;
+    if (int rc = mk::session_enter(s, stream, &st)) return rc;
+    return mk::drain_launch(s, d_sel, m, max_slices, d_out, d_status, d_steps, d_still_open, nullptr, st);
 }
 
 // ---- snapshots: session records out of a set and back (sess_record.h) --------

@@ -80,6 +80,7 @@ class BatchResult:
     out: np.ndarray  # int32: first OUT value (the /compute result), 0 if none
     status: np.ndarray  # uint8: MK_ST_* reason | MK_ST_HAS_OUTPUT
     steps: Optional[np.ndarray]  # uint32 retired node-instructions, if requested
+    still_open: Optional[int] = None  # SessionSet.drain: calls left open at the slice limit
 
     @property
     def has_output(self) -> np.ndarray:
@@ -362,14 +363,14 @@ class SessionSet:
             return self._call("mk_session_step_indexed", sel.size, steps, False, _ptr(sel), sel.size, None)
         return self._call("mk_session_step", self.n, steps, False, None)
 
-    def _call(self, name, shape, steps, busy_ok, *args) -> BatchResult:
+    def _call(self, name, shape, steps, busy_ok, *args, tail=()) -> BatchResult:
         """One host form of the C ABI, ``N.lib().<name>(set, *args, out, status,
-        steps)``, into fresh result arrays of ``shape``.  MkError names
+        steps, *tail)``, into fresh result arrays of ``shape``.  MkError names
         ``name``; MK_EBUSY passes with ``busy_ok``."""
         out = np.zeros(shape, np.int32)
         st = np.zeros(shape, np.uint8)
         sp = np.zeros(shape, np.uint32) if steps else None
-        rc = getattr(N.lib(), name)(self._h, *args, _ptr(out), _ptr(st), _ptr(sp))
+        rc = getattr(N.lib(), name)(self._h, *args, _ptr(out), _ptr(st), _ptr(sp), *tail)
         if not (busy_ok and rc == N.MK_EBUSY):
             N.check(rc, name)
         return BatchResult(out, st, sp)
@@ -398,6 +399,85 @@ class SessionSet:
         op = np.zeros(m, np.uint8)
         N.check(N.lib().mk_session_call_open(self._h, _ptr(sel), m, _ptr(op)), "mk_session_call_open")
         return op
+
+    # ---- open calls (include/mk.h: the list, the device resume and the drain) ----
+    def _listed(self, index_ptr, m) -> int:
+        if (index_ptr is None) != (m is None):
+            raise ValueError("index_ptr and m go together")
+        if m is None:
+            return self.n
+        if not 0 <= m <= self.n:
+            raise ValueError(f"m = {m} outside [0, {self.n}]")
+        return m
+
+    def open_list(self, index=None):
+        """The instances with a call open, found and packed on the GPU
+        (mk_session_open_list): ``(list, pos)``, uint32 arrays of as many
+        entries as there are open calls among all ``n`` instances or the
+        listed ones.  ``list`` is increasing -- itself a valid ``index`` --
+        and ``index[pos[k]] == list[k]`` (without ``index``, ``pos`` is
+        ``list``)."""
+        sel = self._index(index) if index is not None else None
+        m = self.n if sel is None else sel.size
+        lst, pos = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        cnt = C.c_size_t()
+        N.check(N.lib().mk_session_open_list(self._h, _ptr(sel), m, _ptr(lst), _ptr(pos), C.byref(cnt)),
+                "mk_session_open_list")
+        return lst[:cnt.value], pos[:cnt.value]
+
+    def open_list_device(self, list_ptr, pos_ptr, count_ptr, *, stream=None, index_ptr=None, m=None):
+        """:meth:`open_list` into device uint32 arrays of ``m`` entries
+        (``pos_ptr`` may be None) and one count word, asynchronous on
+        ``stream``.  Past the count the list is padded with 0xffffffff and
+        ``pos`` with 0, so the list serves as the ``index_ptr`` of a launch
+        over ``m`` entries without reading the count back.  ``index_ptr`` and
+        ``m`` as in :meth:`compute_device`."""
+        m = self._listed(index_ptr, m)
+        N.check(N.lib().mk_session_open_list_device(self._h, index_ptr, m, list_ptr, pos_ptr, count_ptr, stream),
+                "mk_session_open_list_device")
+
+    def resume_device(self, out_ptr, status_ptr, steps_ptr=None, *, stream=None, index_ptr=None, m=None):
+        """:meth:`resume` on device arrays of ``m`` columns, asynchronous on
+        ``stream`` (mk_session_resume_device); ``index_ptr`` and ``m`` as in
+        :meth:`compute_device`."""
+        m = self._listed(index_ptr, m)
+        N.check(N.lib().mk_session_resume_device(self._h, index_ptr, m, out_ptr, status_ptr, steps_ptr, stream),
+                "mk_session_resume_device")
+
+    def drain(self, *, index=None, max_slices=16, steps=True, promote=False) -> BatchResult:
+        """Finish the open calls of every instance, or of the listed ones:
+        what :meth:`resume` on them, then again on those still at MK_ST_BUDGET,
+        up to ``max_slices`` times in all would report -- each instance the
+        result of its last slice, one without an open call what a resume
+        reports for it (mk_session_drain).  On the GPU every slice runs over a
+        packed list of the calls still open, not over the whole set.
+        ``still_open`` of the result counts the calls left open at the limit.
+        With ``promote`` the instances go back to the native tier afterwards
+        (:meth:`promote` on the same ``index``)."""
+        if int(max_slices) < 1:
+            raise ValueError(f"max_slices = {max_slices}: at least one slice")
+        if int(max_slices) >= 1 << 32:
+            raise ValueError(f"max_slices = {max_slices}: 2^32 or more")
+        sel = self._index(index) if index is not None else None
+        m = self.n if sel is None else sel.size
+        left = C.c_size_t()
+        r = self._call("mk_session_drain", m, steps, False, _ptr(sel), m, int(max_slices), tail=(C.byref(left),))
+        r.still_open = left.value
+        if promote:
+            self.promote(index)
+        return r
+
+    def drain_device(self, max_slices, out_ptr, status_ptr, steps_ptr=None, still_open_ptr=None, *, stream=None,
+                     index_ptr=None, m=None):
+        """:meth:`drain` on device arrays of ``m`` columns, asynchronous on
+        ``stream`` and without any read-back: all ``max_slices`` slices are
+        queued (mk_session_drain_device).  ``still_open_ptr`` (one device
+        uint32, or None) takes the number of calls left open."""
+        if not 1 <= int(max_slices) < 1 << 32:
+            raise ValueError(f"max_slices = {max_slices} outside [1, 2^32)")
+        m = self._listed(index_ptr, m)
+        N.check(N.lib().mk_session_drain_device(self._h, index_ptr, m, int(max_slices), out_ptr, status_ptr,
+                                                steps_ptr, still_open_ptr, stream), "mk_session_drain_device")
 
     def compute_seq(self, values, *, steps=True, busy_ok=False, index=None) -> BatchResult:
         """Sequential /compute calls in one launch: ``values`` has shape
