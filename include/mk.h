@@ -459,6 +459,60 @@ int mk_requests_group_device(int device, uint32_t n, const uint32_t *d_ids, size
                              uint32_t *d_sel, uint32_t *d_off, uint32_t *d_m, void *d_tmp, size_t tmp_bytes,
                              void *stream);
 
+/* ---- served queues: a request queue answered to completion -------------------
+ * A queue as above (`total` < 2^32 requests, request j for session ids[j] with
+ * in[j], answered at position j), served until every call has answered or
+ * used up its slices.  The result is that of this sequence, the requests taken
+ * in arrival order:
+ *   (out, status, steps)[j] = mk_session_compute_indexed({ids[j]}, in[j])
+ *   up to max_slices times while status[j] == MK_ST_BUDGET:
+ *   (out, status, steps)[j] = mk_session_step_indexed({ids[j]}, in = NULL)
+ * so a call gets its own slice and at most max_slices resume slices -- what
+ * mk_session_drain(max_slices) gives it -- and steps accumulate over them as a
+ * resume reports them.  A call still at MK_ST_BUDGET after that stays open: the
+ * later requests of its session report MK_ST_CALL_OPEN and their inputs are not
+ * taken.  A session whose call was open before the serve is never resumed by
+ * it: all its requests report MK_ST_CALL_OPEN and the open call is left exactly
+ * as it was.  After a stack overflow the later requests report
+ * MK_ST_STACK_OVERFLOW with out 0, as in any burst.  A session with no request
+ * is not touched.  total == 0 is MK_OK and launches nothing.
+ *
+ * On the GPU the queue is grouped once and served in rounds: one ragged launch
+ * over the sessions that still have requests to run, the drain over those
+ * whose call hit the budget in it, and the sessions whose drained call
+ * answered go into the next round with the requests behind that call.  Both
+ * forms are ordered against every other launch of the set like the queue
+ * forms.  Their scratch belongs to the set and grows on demand: a call
+ * synchronises only when it has to grow (it never shrinks), and MK_ENOMEM
+ * leaves the set usable.  MK_EDEVICE on a set broken by a failed launch;
+ * MK_EINVAL for max_slices == 0 and for sets of a network with remote peers:
+ * there the host serves the peers between slices, as for the drain.
+ *
+ * The host form is synchronous and runs rounds until no request is left to
+ * run, reading the next round's size back after each, so that a round after
+ * the first costs what the sessions and requests still to run cost, not the
+ * whole queue.  *still_open (nullable) is the number of requests whose final
+ * status is MK_ST_BUDGET, *rounds (nullable) the number of ragged launches
+ * made.  MK_EINVAL for any ids[j] >= n before anything is queued; MK_EBUSY,
+ * like the queue form, when a request that is the first of its session
+ * reported MK_ST_CALL_OPEN. */
+int mk_session_serve(mk_session *s, const uint32_t *ids, const int64_t *in, size_t total, uint32_t max_slices,
+                     int32_t *out, uint8_t *status, uint32_t *steps /* nullable */,
+                     size_t *still_open /* nullable */, size_t *rounds /* nullable */);
+/* Device form, asynchronous on `stream` and without any read-back: exactly
+ * max_rounds >= 1 rounds are queued, every one over the padded full length, as
+ * mk_session_drain_device queues its slices.  A request that no round reached
+ * is unserved: out 0, status 0, steps 0, its input not taken.  The unserved
+ * requests of one session are always a suffix of its requests in arrival
+ * order, so serving the unserved requests again, in their original order,
+ * gives what one serve with enough rounds gives.  d_left (nullable, 2 words):
+ * d_left[0] the number of requests left open, d_left[1] the number unserved.
+ * d_ids is taken ON TRUST; the net: a request with d_ids[j] >= n touches no
+ * session, reports out 0, status 0, steps 0 and is not counted as unserved. */
+int mk_session_serve_device(mk_session *s, const uint32_t *d_ids, const int64_t *d_in, size_t total,
+                            uint32_t max_slices, uint32_t max_rounds, int32_t *d_out, uint8_t *d_status,
+                            uint32_t *d_steps /* nullable */, uint32_t *d_left /* nullable, 2 words */, void *stream);
+
 /* ---- snapshots: a session's state out of the set and back -------------------
  * A session record is one session's whole state -- registers, ports, pending
  * sends, stacks, inChan / outChan, its open call, the tier that holds it --

@@ -507,6 +507,37 @@ func (s *Sessions) Drain(sel []uint32, maxSlices uint32) (r *Result, stillOpen i
 	return r, int(left), nil
 }
 
+// Serve answers a request queue to completion on the GPU: ComputeQueue with
+// every call that outlives its budget slice resumed, up to maxSlices more
+// slices, before the next request of its instance runs.  A call still open
+// after that stays open (MK_ST_BUDGET) and the later requests of its instance
+// report MK_ST_CALL_OPEN.  stillOpen counts the requests left at MK_ST_BUDGET,
+// rounds the ragged launches made (mk_session_serve).
+func (s *Sessions) Serve(ids []uint32, in []int64, maxSlices uint32) (r *Result, stillOpen, rounds int, err error) {
+	total := len(ids)
+	if len(in) != total {
+		return nil, 0, 0, fmt.Errorf("mk: %d inputs for %d requests", len(in), total)
+	}
+	if maxSlices == 0 {
+		return nil, 0, 0, fmt.Errorf("mk: a serve takes at least one slice")
+	}
+	if total == 0 {
+		return &Result{}, 0, 0, nil
+	}
+	if uint64(total) >= 1<<32 {
+		return nil, 0, 0, fmt.Errorf("mk: 2^32 requests or more")
+	}
+	r = &Result{Out: make([]int32, total), Status: make([]uint8, total), Steps: make([]uint32, total)}
+	var left, nr C.size_t
+	rc := C.mk_session_serve(s.s, (*C.uint32_t)(unsafe.Pointer(&ids[0])), (*C.int64_t)(unsafe.Pointer(&in[0])),
+		C.size_t(total), C.uint32_t(maxSlices), (*C.int32_t)(unsafe.Pointer(&r.Out[0])),
+		(*C.uint8_t)(unsafe.Pointer(&r.Status[0])), (*C.uint32_t)(unsafe.Pointer(&r.Steps[0])), &left, &nr)
+	if rc != C.MK_OK {
+		return nil, 0, 0, fmt.Errorf("mk_session_serve: %d", int(rc))
+	}
+	return r, int(left), int(nr), nil
+}
+
 // Promote hands the listed instances that the interpreter holds between calls
 // back to the native tier (sel nil: all n) and reports, in list order, which
 // were promoted -- mk_session_promote.  An instance with a call open, one the

@@ -161,6 +161,12 @@ SIGNATURES = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mk_session_compute_queue_device": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_serve": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "mk_session_serve_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "mk_requests_group_tmp_bytes": (C.c_int, [C.c_uint32, C.c_size_t, C.POINTER(C.c_size_t)]),
     "mk_requests_group_device": (
         C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

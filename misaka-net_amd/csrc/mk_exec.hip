@@ -3090,6 +3090,7 @@ void *pick_session_kernel(int nprog, bool sel = false)
 } // namespace mk
 
 #include "sess_drain.h"
+#include "sess_serve.h"
 
 struct mk_session {
     mk_net *h = nullptr;
@@ -3115,6 +3116,12 @@ struct mk_session {
     void *d_drain = nullptr;
     size_t drain_cap = 0;
     uint32_t *h_drain = nullptr;
+    // served queues (mk_session_serve, sess_serve.h): the round lists, the
+    // drain list with its columns, the compact inputs of a later round and the
+    // counters, one allocation with room for serve_cap requests, grown on
+    // demand; the grouping and the compact outputs are the queue scratch's
+    void *d_serve = nullptr;
+    size_t serve_cap = 0;
     hipStream_t stream = nullptr;
     mk::SessParams p{};
     // native tier (tis_jit.h mk_sess_exec): the session schedule compiled to
@@ -3177,6 +3184,7 @@ struct mk_session {
         (void)hipFree(d_queue);
         (void)hipFree(d_drain);
         (void)hipHostFree(h_drain);
+        (void)hipFree(d_serve);
         mk::release_module(mod);
         if (order) (void)hipEventDestroy(order);
         if (stream) (void)hipStreamDestroy(stream);
@@ -3837,8 +3845,12 @@ int open_list_launch(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t *d
 // Otherwise the host form (st is s->stream): the count read back after every
 // fold, the next slice over that many entries, none at 0; *left takes the
 // last.  Caller as for queue_launch; 1 <= m <= n < 2^32, max_slices >= 1.
+// Inside a serve (serve_launch) `mark` is false, the serve marks the set once
+// at its end, and *opened (host form, when given) takes the number of calls
+// that were open at the start.
 int drain_launch(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t max_slices, int32_t *d_out,
-                 uint8_t *d_status, uint32_t *d_steps, uint32_t *d_still, size_t *left, hipStream_t st)
+                 uint8_t *d_status, uint32_t *d_steps, uint32_t *d_still, size_t *left, hipStream_t st,
+                 bool mark = true, size_t *opened = nullptr)
 {
     if (s->broken) return MK_EDEVICE;
     if (int rc = drain_reserve(s, m)) return rc;
@@ -3858,7 +3870,11 @@ int drain_launch(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t max_sl
     uint32_t len = (uint32_t)m;
     int cur = 0;
     for (uint32_t k = 0; rc == MK_OK && k < max_slices; k++) {
-        if (left && ((rc = count(&len)) != MK_OK || len == 0)) break;
+        if (left) {
+            rc = count(&len);
+            if (opened && k == 0 && rc == MK_OK) *opened = len;
+            if (rc != MK_OK || len == 0) break;
+        }
         SessCall c = SessCall::io(d.in, d.out, d.status, d_steps ? d.steps : nullptr);
         c.resume = true;
         c.sel = d.list[cur];
@@ -3873,6 +3889,180 @@ int drain_launch(mk_session *s, const uint32_t *d_sel, size_t m, uint32_t max_sl
         if (len) rc = count(&len);
         *left = len;
     }
+    if (queued && mark) {
+        const int mr = session_mark(s, st);
+        if (rc == MK_OK) rc = mr;
+    }
+    return rc;
+}
+
+// The serve scratch of a set, for `total` requests (sess_serve.h); M entries.
+struct ServeBufs {
+    uint32_t *sel[2], *beg[2], *off[2]; // the round list a round runs over and the one it packs
+    uint32_t *npos;                     // the drain slot of each slot of the list being packed
+    uint32_t *hit;                      // per round slot: where its call hit the budget
+    uint32_t *dlist, *dpos;             // the drain list
+    int32_t *dout;                      // the drain's columns
+    uint32_t *dsteps;
+    uint8_t *dstatus;
+    uint32_t *words, *sums, *cnt;
+    int64_t *in; // the compact inputs of a round after the first
+    size_t bytes;
+};
+
+ServeBufs serve_layout(size_t n, size_t total, void *base)
+{
+    const size_t M = total < n ? total : n;
+    Carver k(base);
+    ServeBufs v{};
+    for (int b = 0; b < 2; b++) {
+        v.sel[b] = k.take<uint32_t>(M);
+        v.beg[b] = k.take<uint32_t>(M);
+        v.off[b] = k.take<uint32_t>(M + 1);
+    }
+    v.npos = k.take<uint32_t>(M);
+    v.hit = k.take<uint32_t>(M);
+    v.dlist = k.take<uint32_t>(M);
+    v.dpos = k.take<uint32_t>(M);
+    v.dout = k.take<int32_t>(M);
+    v.dsteps = k.take<uint32_t>(M);
+    v.dstatus = k.take<uint8_t>(M);
+    v.words = k.take<uint32_t>(M + 1);
+    v.sums = k.take<uint32_t>(rg::rg_scan_blocks(M + 1));
+    v.cnt = k.take<uint32_t>(sv::kCntWords);
+    v.in = k.take<int64_t>(total);
+    v.bytes = k.at;
+    return v;
+}
+
+// Room for a serve of `total` requests in the queue, drain and serve scratch,
+// as queue_reserve: growing waits for the set's last launch, a failed
+// allocation leaves the set without that scratch and usable.  Caller holds
+// s->mu and has the device current.
+int serve_reserve(mk_session *s, size_t total)
+{
+    if (int rc = queue_reserve(s, total)) return rc;
+    if (int rc = drain_reserve(s, std::min(total, s->n))) return rc;
+    if (total <= s->serve_cap) return MK_OK;
+    if (s->last && s->order && hipEventSynchronize(s->order) != hipSuccess) return MK_EDEVICE;
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
+    (void)hipFree(s->d_serve);
+    s->d_serve = nullptr;
+    s->serve_cap = 0;
+    const size_t cap = std::min<size_t>(std::max<size_t>(total + total / 2, 4096), 0xffffffffull);
+    if (hipMalloc(&s->d_serve, serve_layout(s->n, cap, nullptr).bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        s->d_serve = nullptr;
+        return MK_ENOMEM;
+    }
+    s->serve_cap = cap;
+    return MK_OK;
+}
+
+// The serve on `st` (sess_serve.h has the rounds).  max_rounds 0 is the host
+// form (st is s->stream): after every round the numbers of slots and requests
+// of the next one are read back, its launches cover those alone, and the loop
+// ends when none is left; the drain inside is the host one, which reads its
+// own count a slice.  *still_open and *rounds take the calls left open and the
+// ragged launches made.  Otherwise the device form: max_rounds rounds over
+// the padded lengths, nothing read back, d_left (nullable) written at the end.
+// Caller as for queue_launch; total in [1, 2^32), 1 <= s->n < 2^32,
+// max_slices >= 1.  d_busy: sv_fold's flag, or null.
+int serve_launch(mk_session *s, const uint32_t *d_ids, const int64_t *d_in, size_t total, uint32_t max_slices,
+                 uint32_t max_rounds, int32_t *d_out, uint8_t *d_status, uint32_t *d_steps, uint32_t *d_busy,
+                 uint32_t *d_left, size_t *still_open, size_t *rounds, hipStream_t st)
+{
+    if (s->broken) return MK_EDEVICE;
+    if (int rc = serve_reserve(s, total)) return rc;
+    const bool host = max_rounds == 0;
+    const QueueBufs q = queue_layout(s->n, s->queue_cap, s->d_queue);
+    const ServeBufs v = serve_layout(s->n, s->serve_cap, s->d_serve);
+    const uint32_t n = (uint32_t)s->n, tot = (uint32_t)total;
+    const dim3 blk(rg::kRgBlock);
+    auto launched = [] { return hipGetLastError() == hipSuccess ? (int)MK_OK : (int)MK_EDEVICE; };
+    // whatever gets queued reads and writes the scratch: a later launch that grows it must wait
+    bool queued = true;
+    int rc = MK_OK;
+    // a request no round reaches, or whose id names no session, reports 0 / 0 / 0
+    if (hipMemsetAsync(d_out, 0, total * 4, st) != hipSuccess || hipMemsetAsync(d_status, 0, total, st) != hipSuccess ||
+        (d_steps && hipMemsetAsync(d_steps, 0, total * 4, st) != hipSuccess) ||
+        hipMemsetAsync(v.cnt, 0, sv::kCntWords * 4, st) != hipSuccess)
+        rc = MK_EDEVICE;
+    if (rc == MK_OK) rc = rg::rg_group(n, d_ids, tot, q.perm, q.sel, q.off, q.m, q.tmp, st);
+    if (rc == MK_OK) {
+        hipLaunchKernelGGL(rg::rq_gather, dim3(sv::sv_blocks(total)), blk, 0, st, d_in, (const uint32_t *)q.perm, tot,
+                           q.in);
+        rc = launched();
+    }
+    uint32_t *const c_steps = d_steps ? q.steps : nullptr, *const dsteps = d_steps ? v.dsteps : nullptr;
+    // the first round's list is the grouping: a slot's requests start where its compact words do
+    sv::SvList cur{q.sel, q.off, q.off};
+    const int64_t *c_in = q.in;
+    uint32_t len = (uint32_t)std::min(total, s->n), req = tot; // slots and requests the launches cover
+    size_t open = 0, nr = 0;
+    for (uint32_t r = 0; rc == MK_OK && (host || r < max_rounds); r++) {
+        SessCall k = SessCall::io(c_in, q.out, q.status, c_steps);
+        k.sel = cur.sel;
+        k.m = len;
+        k.off = cur.off;
+        k.total = req;
+        if ((rc = session_launch(s, k, st, &queued)) != MK_OK) break;
+        ++nr;
+        hipLaunchKernelGGL(sv::sv_fold, dim3(sv::sv_blocks(req)), blk, 0, st, cur, len, (const uint32_t *)q.perm, tot,
+                           (const int32_t *)q.out, (const uint8_t *)q.status, (const uint32_t *)c_steps, d_out,
+                           d_status, d_steps, r == 0 ? d_busy : nullptr);
+        if ((rc = launched()) != MK_OK) break;
+        const sv::SvHit hit{cur, n, tot, q.status, v.hit};
+        if ((rc = dr::dr_compact(hit, len, v.dlist, v.dpos, v.cnt + sv::kHit, nullptr, v.words, v.sums, st)) != MK_OK)
+            break;
+        size_t left = 0, opened = len;
+        rc = drain_launch(s, v.dlist, len, max_slices, v.dout, v.dstatus, dsteps, v.cnt + sv::kStill,
+                          host ? &left : nullptr, st, false, host ? &opened : nullptr);
+        if (rc != MK_OK) break;
+        open += left;
+        if (host && opened == 0) break; // no call outlived its slice: every request is answered
+        hipLaunchKernelGGL(sv::sv_advance, dim3(sv::sv_blocks(len)), blk, 0, st, (const uint32_t *)v.dlist,
+                           (const uint32_t *)v.dpos, len, n, (const uint32_t *)v.hit, (const uint32_t *)q.perm, tot,
+                           (const int32_t *)v.dout, (const uint8_t *)v.dstatus, (const uint32_t *)dsteps, d_out,
+                           d_status, d_steps, v.cnt);
+        if ((rc = launched()) != MK_OK) break;
+        const int b = (int)(r & 1u);
+        const sv::SvNext next{v.dlist, v.dpos, n, v.dstatus, v.hit, cur};
+        if ((rc = dr::dr_compact(next, len, v.sel[b], v.npos, v.cnt + sv::kPend, nullptr, v.words, v.sums, st)) !=
+            MK_OK)
+            break;
+        hipLaunchKernelGGL(sv::sv_next, dim3(sv::sv_blocks((uint64_t)len + 1)), blk, 0, st, (const uint32_t *)v.sel[b],
+                           (const uint32_t *)v.npos, len, n, (const uint32_t *)v.dpos, (const uint32_t *)v.hit, cur,
+                           v.beg[b], v.off[b]);
+        if ((rc = launched()) != MK_OK) break;
+        if ((rc = rg::rg_scan(v.off[b], (uint64_t)len + 1, v.sums, v.cnt + sv::kReq, st)) != MK_OK) break;
+        cur = sv::SvList{v.sel[b], v.beg[b], v.off[b]};
+        if (host) {
+            if (hipMemcpyAsync(s->h_drain, v.cnt + sv::kPend, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess) {
+                rc = MK_EDEVICE;
+                break;
+            }
+            // the list is packed: its first kPend slots hold all kReq requests, off[kPend] their number
+            len = std::min(len, s->h_drain[sv::kPend]);
+            req = std::min(req, s->h_drain[sv::kReq]);
+            if (len == 0 || req == 0) break;
+        } else if (r + 1 == max_rounds) {
+            break; // no round runs this list: sv_unserved below
+        }
+        hipLaunchKernelGGL(sv::sv_gather, dim3(sv::sv_blocks(req)), blk, 0, st, cur, len, (const int64_t *)q.in, tot,
+                           v.in);
+        rc = launched();
+        c_in = v.in;
+    }
+    if (rc == MK_OK && !host) {
+        // cur: the list the last round packed
+        hipLaunchKernelGGL(sv::sv_unserved, dim3(sv::sv_blocks(std::max<uint32_t>(req, 1u))), blk, 0, st, cur, len,
+                           (const uint32_t *)q.perm, tot, d_out, d_status, d_steps, (const uint32_t *)v.cnt, d_left);
+        rc = launched();
+    }
+    if (still_open) *still_open = open;
+    if (rounds) *rounds = nr;
     if (queued) {
         const int mr = session_mark(s, st);
         if (rc == MK_OK) rc = mr;
@@ -4814,6 +5004,64 @@ int mk_session_drain_device(mk_session *s, const uint32_t *d_sel, size_t m, uint
     hipStream_t st;
     if (int rc = mk::session_enter(s, stream, &st)) return rc;
     return mk::drain_launch(s, d_sel, m, max_slices, d_out, d_status, d_steps, d_still_open, nullptr, st);
+}
+
+// ---- served queues: a request queue answered to completion (sess_serve.h) -----
+int mk_session_serve(mk_session *s, const uint32_t *ids, const int64_t *in, size_t total, uint32_t max_slices,
+                     int32_t *out, uint8_t *status, uint32_t *steps, size_t *still_open, size_t *rounds)
+{
+    if (!s || max_slices == 0 || (total && (!ids || !in || !out || !status))) return MK_EINVAL;
+    if (total > 0xffffffffull) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->p.mixed) return MK_EINVAL; // the host serves the peers between slices, as for the drain
+    for (size_t j = 0; j < total; j++)
+        if (ids[j] >= s->n) return MK_EINVAL;
+    if (still_open) *still_open = 0;
+    if (rounds) *rounds = 0;
+    if (total == 0) return MK_OK;
+    if (s->n > 0xffffffffull) return MK_ELIMIT;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    uint32_t busy = 0;
+    size_t open = 0, nr = 0;
+    mk::HostIO io = mk::HostIO::of(total, in, out, status, steps);
+    io.ids = ids;
+    io.flag = &busy;
+    int rc = mk::session_round_trip(s, io, [&](const mk::StageDev &d) {
+        return mk::serve_launch(s, d.ids, d.in, total, max_slices, 0, d.out, d.status, d.steps, d.flag, nullptr, &open,
+                                &nr, s->stream);
+    });
+    if (rc) return rc;
+    if (still_open) *still_open = open;
+    if (rounds) *rounds = nr;
+    // the first request of a session that had a call open when the serve began did nothing
+    return busy ? MK_EBUSY : MK_OK;
+}
+
+int mk_session_serve_device(mk_session *s, const uint32_t *d_ids, const int64_t *d_in, size_t total,
+                            uint32_t max_slices, uint32_t max_rounds, int32_t *d_out, uint8_t *d_status,
+                            uint32_t *d_steps, uint32_t *d_left, void *stream)
+{
+    if (!s || max_slices == 0 || max_rounds == 0 || (total && (!d_ids || !d_in || !d_out || !d_status)))
+        return MK_EINVAL;
+    if (total > 0xffffffffull || s->p.mixed) return MK_EINVAL;
+    if (total == 0) return MK_OK;
+    if (s->n > 0xffffffffull) return MK_ELIMIT;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::DeviceGuard g(s->device);
+    hipStream_t st;
+    if (int rc = mk::session_enter(s, stream, &st)) return rc;
+    if (s->n == 0) { // no id names a session
+        if (s->broken) return MK_EDEVICE;
+        if (hipMemsetAsync(d_out, 0, total * 4, st) != hipSuccess ||
+            hipMemsetAsync(d_status, 0, total, st) != hipSuccess ||
+            (d_steps && hipMemsetAsync(d_steps, 0, total * 4, st) != hipSuccess) ||
+            (d_left && hipMemsetAsync(d_left, 0, 8, st) != hipSuccess))
+            return MK_EDEVICE;
+        return MK_OK;
+    }
+    return mk::serve_launch(s, d_ids, d_in, total, max_slices, max_rounds, d_out, d_status, d_steps, nullptr, d_left,
+                            nullptr, nullptr, st);
 }
 
 // ---- snapshots: session records out of a set and back (sess_record.h) --------

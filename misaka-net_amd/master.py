@@ -265,6 +265,11 @@ class MasterNode:
         burst's calls that did not run answer no output (MK_ST_BUDGET).  The
         burst's later calls, which did not run behind an open call
         (MK_ST_CALL_OPEN), go in the next launch."""
+        # SessionSet.serve (mk_session_serve) is this loop for a set of many
+        # instances, run on the GPU: burst, drain, and what stood behind the
+        # drained calls in the next round.  The master keeps the host loop: its
+        # per-slice deadline, /pause and the epoch checks need the host
+        # between slices.
         deadline = None if self.call_timeout is None else time.monotonic() + self.call_timeout
         res: list = []
         with self._burst:

@@ -80,7 +80,8 @@ class BatchResult:
     out: np.ndarray  # int32: first OUT value (the /compute result), 0 if none
     status: np.ndarray  # uint8: MK_ST_* reason | MK_ST_HAS_OUTPUT
     steps: Optional[np.ndarray]  # uint32 retired node-instructions, if requested
-    still_open: Optional[int] = None  # SessionSet.drain: calls left open at the slice limit
+    still_open: Optional[int] = None  # SessionSet.drain and serve: calls left open at the slice limit
+    rounds: Optional[int] = None  # SessionSet.serve: ragged launches made
 
     @property
     def has_output(self) -> np.ndarray:
@@ -652,6 +653,57 @@ class SessionSet:
         N.check(N.lib().mk_session_compute_queue_device(self._h, ids_ptr, in_ptr, total, out_ptr, status_ptr,
                                                         steps_ptr, stream),
                 "mk_session_compute_queue_device")
+
+    # ---- served queues (include/mk.h: a request queue answered to completion) ----
+    @staticmethod
+    def _slices(name, value):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+            raise ValueError(f"{name} = {value!r} is not an integer")
+        if not 1 <= int(value) < 1 << 32:
+            raise ValueError(f"{name} = {value} outside [1, 2^32)")
+        return int(value)
+
+    def serve(self, ids, values, *, max_slices=16, steps=True, busy_ok=False, promote=False) -> BatchResult:
+        """A request queue served to completion on the GPU: what
+        :meth:`compute_queue` answers when every call that outlives its budget
+        slice is resumed, up to ``max_slices`` more slices as :meth:`drain`
+        gives it, before the next request of its instance runs -- the requests
+        of one instance one at a time, each waiting for its answer
+        (mk_session_serve).  A call still open after its slices stays open
+        (MK_ST_BUDGET) and the later requests of its instance report
+        MK_ST_CALL_OPEN; an instance whose call was open beforehand is not
+        resumed, all its requests report MK_ST_CALL_OPEN, and this raises
+        MkError(MK_EBUSY) unless ``busy_ok``.  ``still_open`` of the result
+        counts the requests left at MK_ST_BUDGET, ``rounds`` the ragged
+        launches made.  With ``promote`` the instances go back to the native
+        tier afterwards (:meth:`promote` on the whole set)."""
+        k = SessionSet._slices("max_slices", max_slices)
+        q, v = SessionSet._queue(self, ids, values)
+        left, rounds = C.c_size_t(), C.c_size_t()
+        r = self._call("mk_session_serve", q.size, steps, busy_ok, _ptr(q), _ptr(v), q.size, k,
+                       tail=(C.byref(left), C.byref(rounds)))
+        r.still_open, r.rounds = left.value, rounds.value
+        if promote:
+            self.promote()
+        return r
+
+    def serve_device(self, ids_ptr, in_ptr, total, max_slices, max_rounds, out_ptr, status_ptr, steps_ptr=None,
+                     left_ptr=None, *, stream=None):
+        """:meth:`serve` on device arrays of ``total`` words each, asynchronous
+        on ``stream`` and without any read-back: exactly ``max_rounds`` rounds
+        are queued (mk_session_serve_device).  A request no round reached is
+        unserved and reports 0 / 0 / 0; the unserved requests of an instance
+        are the last of its requests, so serving them again in order continues
+        the queue.  ``left_ptr`` (two device uint32, or None) takes the numbers
+        of requests left open and unserved.  The ids (uint32) are taken on
+        trust; one that is ``>= n`` touches no instance, reports 0 / 0 / 0 and
+        is not counted."""
+        k = SessionSet._slices("max_slices", max_slices)
+        nr = SessionSet._slices("max_rounds", max_rounds)
+        if not 0 <= total < 1 << 32:
+            raise ValueError(f"total = {total} outside [0, 2^32)")
+        N.check(N.lib().mk_session_serve_device(self._h, ids_ptr, in_ptr, total, k, nr, out_ptr, status_ptr, steps_ptr,
+                                                left_ptr, stream), "mk_session_serve_device")
 
     def reset(self, *, index=None):
         """/reset (master.go:126-143): every instance back to its initial
