@@ -513,6 +513,105 @@ int mk_session_serve_device(mk_session *s, const uint32_t *d_ids, const int64_t 
                             uint32_t max_slices, uint32_t max_rounds, int32_t *d_out, uint8_t *d_status,
                             uint32_t *d_steps /* nullable */, uint32_t *d_left /* nullable, 2 words */, void *stream);
 
+/* ---- client keys: a directory from 64-bit keys to instances ------------------
+ * A server names its clients by connection ids, user ids or hashes, not by
+ * instance numbers.  A set has at most one directory: a partial injective map
+ * from uint64_t keys to the set's instances, and a FIFO of the free instances,
+ * both on the GPU.  MK_KEY_NONE is never bound; every other key is valid.
+ *
+ *   open     the set is reset as mk_session_reset resets it, every instance is
+ *            free, and the FIFO is 0, 1, ..., n-1.
+ *   bind     keys[0..total) in arrival order to ids[0..total).  A key bound
+ *            before the call gives its instance.  The distinct keys that are not
+ *            bound are the new keys, in the order of their first occurrence in
+ *            this queue: the k-th of them takes the k-th instance from the front
+ *            of the FIFO.  When the FIFO runs out the remaining new keys are
+ *            rejected: they stay unbound and every one of their requests gets
+ *            0xffffffff.  A MK_KEY_NONE request gets 0xffffffff and is counted
+ *            nowhere.  counts = {keys admitted, keys rejected, requests of
+ *            rejected keys}.  An admitted instance is in the post-/reset state:
+ *            open and release keep every free instance there.  0xffffffff is
+ *            what the queue and serve forms treat as "touches no session".
+ *   lookup   as bind, but nothing is admitted: an unbound key gives 0xffffffff.
+ *   release  every listed key that is bound loses its binding; its instance is
+ *            reset as mk_session_reset_indexed resets it, once, and goes to the
+ *            back of the FIFO, the instances of one release in increasing
+ *            order.  Unbound keys, MK_KEY_NONE and repeats are ignored.
+ *   export   owner[i] = the key of instance i, MK_KEY_NONE for a free one.
+ *   import   replaces the whole directory by such an array and resets nothing;
+ *            the FIFO is then the free instances in increasing order.
+ *            MK_EINVAL, and nothing changes, when a key occurs twice.  With
+ *            snapshot and restore this carries a keyed set to another set or
+ *            process.
+ *
+ * The directory never looks at instance state, and mk_session_reset leaves the
+ * bindings in place.  The ids depend on nothing but the contract above: not on
+ * the order in which the GPU's threads run.  Bind and lookup cost what `total`
+ * requests cost and never pass over the n instances; a release costs what its
+ * m listed keys cost, and now and then -- after releases that listed a quarter
+ * of the table's slots in all, bound or not -- a rebuild of the table over the n instances, so deletions
+ * never degrade it (info.tombstones <= info.slots / 4 after every release).
+ * The table is open addressing with linear probing in mk_session_dir_slots(n)
+ * slots of 12 bytes, the power of two that is at least 2n; with the owner
+ * array and the FIFO that is 36 to 60 bytes an instance.  MK_ELIMIT for sets
+ * of more than 2^30 instances.
+ *
+ * Every operation is ordered against every other launch of the set like the
+ * indexed forms.  MK_EINVAL without a directory (and for a second open), for
+ * total or m >= 2^32 and for null arrays; MK_EDEVICE on a set broken by a failed
+ * launch; total == 0 and m == 0 are MK_OK and launch nothing.  The scratch
+ * belongs to the set and grows on demand: a call synchronises only when it has
+ * to grow (it never shrinks), and MK_ENOMEM leaves the set usable.  The host
+ * forms are synchronous; the device forms are asynchronous on `stream`, read
+ * nothing back and take their arrays ON TRUST. */
+#define MK_KEY_NONE 0xffffffffffffffffull
+typedef struct {
+    uint32_t slots, live, free, tombstones;
+} mk_session_dir_info;
+
+int mk_session_dir_open(mk_session *s);
+int mk_session_dir_close(mk_session *s); /* also freed with the set */
+int mk_session_dir_info_get(mk_session *s, mk_session_dir_info *out);
+int mk_session_dir_export(mk_session *s, uint64_t *owner /* n */);
+int mk_session_dir_import(mk_session *s, const uint64_t *owner /* n */);
+
+int mk_session_bind(mk_session *s, const uint64_t *keys, size_t total, uint32_t *ids,
+                    size_t counts[3] /* nullable */);
+int mk_session_bind_device(mk_session *s, const uint64_t *d_keys, size_t total, uint32_t *d_ids,
+                           uint32_t *d_counts /* nullable, 3 words */, void *stream);
+int mk_session_lookup(mk_session *s, const uint64_t *keys, size_t total, uint32_t *ids);
+int mk_session_lookup_device(mk_session *s, const uint64_t *d_keys, size_t total, uint32_t *d_ids, void *stream);
+int mk_session_release(mk_session *s, const uint64_t *keys, size_t m, size_t *released /* nullable */);
+int mk_session_release_device(mk_session *s, const uint64_t *d_keys, size_t m,
+                              uint32_t *d_released /* nullable */, void *stream);
+
+/* Bind, then the queue / the serve on the ids, the keys staged once; ids
+ * (nullable) returns the assignment.  Rejected and MK_KEY_NONE requests are
+ * unserved (out 0, status 0, steps 0), not MK_EINVAL; everything else as the
+ * unkeyed host forms, MK_EBUSY included.  On the device the same is
+ * mk_session_bind_device followed by mk_session_compute_queue_device or
+ * mk_session_serve_device on the ids. */
+int mk_session_compute_queue_keyed(mk_session *s, const uint64_t *keys, const int64_t *in, size_t total,
+                                   int32_t *out, uint8_t *status, uint32_t *steps /* nullable */,
+                                   uint32_t *ids /* nullable */, size_t counts[3] /* nullable */);
+int mk_session_serve_keyed(mk_session *s, const uint64_t *keys, const int64_t *in, size_t total,
+                           uint32_t max_slices, int32_t *out, uint8_t *status, uint32_t *steps /* nullable */,
+                           uint32_t *ids /* nullable */, size_t counts[3] /* nullable */,
+                           size_t *still_open /* nullable */, size_t *rounds /* nullable */);
+
+/* The device form of mk_session_reset_indexed, asynchronous on `stream`: d_sel
+ * is taken ON TRUST (strictly increasing); an entry >= n touches nothing.
+ * MK_EDEVICE on a set broken by a failed launch: only the host forms, which can
+ * see that a list names all n sessions, mend such a set. */
+int mk_session_reset_indexed_device(mk_session *s, const uint32_t *d_sel, size_t m, void *stream);
+
+/* Pure host functions, usable without a GPU: the table size for n instances
+ * (MK_EINVAL for n == 0, MK_ELIMIT above 2^30) and the slot each key's probe
+ * starts at in a table of `slots` slots (a power of two), so that tests can
+ * build colliding keys. */
+int mk_session_dir_slots(size_t n, uint32_t *slots);
+int mk_session_dir_home(const uint64_t *keys, size_t m, uint32_t slots, uint32_t *home);
+
 /* ---- snapshots: a session's state out of the set and back -------------------
  * A session record is one session's whole state -- registers, ports, pending
  * sends, stacks, inChan / outChan, its open call, the tier that holds it --

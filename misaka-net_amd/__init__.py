@@ -8,11 +8,16 @@ Import name: ``misaka_net_amd`` (a symlink to this directory).
 from . import _native
 from .network import (
     BatchResult,
+    KEY_NONE,
+    NO_INSTANCE,
     Network,
     NodeSpec,
+    SessionDirectory,
     SessionSet,
     SessionSnapshot,
     TisParseError,
+    directory_home,
+    directory_slots,
     generate_inputs_device,
     group_requests_device,
     group_requests_tmp_bytes,
@@ -25,9 +30,14 @@ __all__ = [
     "BatchResult",
     "Network",
     "NodeSpec",
+    "SessionDirectory",
     "SessionSet",
     "SessionSnapshot",
     "TisParseError",
+    "KEY_NONE",
+    "NO_INSTANCE",
+    "directory_home",
+    "directory_slots",
     "generate_inputs_device",
     "group_requests_device",
     "group_requests_tmp_bytes",

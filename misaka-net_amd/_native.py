@@ -100,6 +100,12 @@ class mk_session_layout(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class mk_session_dir_info(C.Structure):
+    _fields_ = [("slots", C.c_uint32), ("live", C.c_uint32), ("free", C.c_uint32), ("tombstones", C.c_uint32)]
+
+
+MK_KEY_NONE = (1 << 64) - 1
+
 # name -> (restype, argtypes); every symbol include/mk.h declares.
 SIGNATURES = {
     "mk_net_load": (C.c_int, [C.POINTER(mk_node_desc), C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]),
@@ -171,6 +177,26 @@ SIGNATURES = {
     "mk_requests_group_device": (
         C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mk_session_dir_open": (C.c_int, [C.c_void_p]),
+    "mk_session_dir_close": (C.c_int, [C.c_void_p]),
+    "mk_session_dir_info_get": (C.c_int, [C.c_void_p, C.POINTER(mk_session_dir_info)]),
+    "mk_session_dir_export": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mk_session_dir_import": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mk_session_bind": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mk_session_bind_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mk_session_lookup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mk_session_release": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "mk_session_release_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mk_session_compute_queue_keyed": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p]),
+    "mk_session_serve_keyed": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "mk_session_reset_indexed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mk_session_dir_slots": (C.c_int, [C.c_size_t, C.POINTER(C.c_uint32)]),
+    "mk_session_dir_home": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "mk_session_layout_get": (C.c_int, [C.c_void_p, C.POINTER(mk_session_layout)]),
     "mk_session_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mk_session_snapshot_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),

@@ -3091,6 +3091,7 @@ void *pick_session_kernel(int nprog, bool sel = false)
 
 #include "sess_drain.h"
 #include "sess_serve.h"
+#include "sess_dir.h"
 
 struct mk_session {
     mk_net *h = nullptr;
@@ -3122,6 +3123,8 @@ struct mk_session {
     // demand; the grouping and the compact outputs are the queue scratch's
     void *d_serve = nullptr;
     size_t serve_cap = 0;
+    // client keys (mk_session_dir_open, sess_dir.h): the directory, null until opened
+    mk::sd::SdDir *dir = nullptr;
     hipStream_t stream = nullptr;
     mk::SessParams p{};
     // native tier (tis_jit.h mk_sess_exec): the session schedule compiled to
@@ -3185,6 +3188,7 @@ struct mk_session {
         (void)hipFree(d_drain);
         (void)hipHostFree(h_drain);
         (void)hipFree(d_serve);
+        mk::sd::sd_dir_free(dir);
         mk::release_module(mod);
         if (order) (void)hipEventDestroy(order);
         if (stream) (void)hipStreamDestroy(stream);
@@ -3535,6 +3539,10 @@ struct HostIO {
     size_t m = 0;
     const uint32_t *sel = nullptr, *off = nullptr, *ids = nullptr;
     uint32_t *flag = nullptr; // receives the device flag, cleared before the launch
+    // a keyed queue: keys[c] go up behind everything else, the launch fills the
+    // ids' room on the device, and ids_back (nullable) receives them
+    const uint64_t *keys = nullptr;
+    uint32_t *ids_back = nullptr;
     static HostIO of(size_t c, const int64_t *in, int32_t *out, uint8_t *status, uint32_t *steps)
     {
         HostIO io;
@@ -3556,6 +3564,7 @@ struct StageDev {
     uint32_t *steps;
     const uint32_t *sel, *off, *ids;
     uint32_t *flag;
+    const uint64_t *keys; // a keyed queue's; ids is then room to fill
 };
 
 // The round trip of a host form through the staging and its pinned mirror
@@ -3567,8 +3576,9 @@ struct StageDev {
 template <class Launch>
 int session_round_trip(mk_session *s, const HostIO &io, Launch launch)
 {
-    const StageLayout L = stage_layout(io.c, io.m, io.sel, io.off, io.ids, io.flag);
-    if (int rc = session_stage(s, L.bytes)) return rc;
+    const StageLayout L = stage_layout(io.c, io.m, io.sel, io.off, io.ids || io.keys, io.flag);
+    const size_t o_keys = L.bytes; // behind the layout every form shares
+    if (int rc = session_stage(s, L.bytes + (io.keys ? Carver::al(io.c * 8) : 0))) return rc;
     char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
     const hipStream_t st = s->stream;
     auto up = [&](size_t at, size_t bytes) {
@@ -3583,15 +3593,17 @@ int session_round_trip(mk_session *s, const HostIO &io, Launch launch)
     if (io.off) memcpy(hb + L.off, io.off, (m + 1) * 4);
     if (io.sel) memcpy(hb + L.sel, io.sel, m * 4);
     if (io.ids) memcpy(hb + L.ids, io.ids, c * 4);
-    if (!up(L.in, c * 8) || (io.off && !up(L.off, (m + 1) * 4)) || (io.sel && !up(L.sel, m * 4)) ||
+    if (io.keys) memcpy(hb + o_keys, io.keys, c * 8);
+    if ((io.keys && !up(o_keys, c * 8)) || !up(L.in, c * 8) || (io.off && !up(L.off, (m + 1) * 4)) || (io.sel && !up(L.sel, m * 4)) ||
         (io.ids && !up(L.ids, c * 4)) || (io.flag && hipMemsetAsync(b + L.flag, 0, 4, st) != hipSuccess))
         return MK_EDEVICE;
     auto u32 = [&](const void *given, size_t at) { return given ? (uint32_t *)(b + at) : nullptr; };
     const StageDev d{(const int64_t *)(b + L.in), (int32_t *)(b + L.out), (uint8_t *)(b + L.status),
-                     u32(io.steps, L.steps), u32(io.sel, L.sel), u32(io.off, L.off), u32(io.ids, L.ids),
-                     u32(io.flag, L.flag)};
+                     u32(io.steps, L.steps), u32(io.sel, L.sel), u32(io.off, L.off),
+                     u32(io.ids ? (const void *)io.ids : (const void *)io.keys, L.ids), u32(io.flag, L.flag),
+                     io.keys ? (const uint64_t *)(b + o_keys) : nullptr};
     if (int rc = launch(d)) return rc;
-    if (!down(L.out, c * 4) || !down(L.status, c) || (io.flag && !down(L.flag, 4)) ||
+    if ((io.ids_back && !down(L.ids, c * 4)) || !down(L.out, c * 4) || !down(L.status, c) || (io.flag && !down(L.flag, 4)) ||
         (io.steps && !down(L.steps, c * 4)))
         return MK_EDEVICE;
     if (hipStreamSynchronize(st) != hipSuccess) return MK_EDEVICE;
@@ -3599,6 +3611,7 @@ int session_round_trip(mk_session *s, const HostIO &io, Launch launch)
     memcpy(io.status, hb + L.status, c);
     if (io.steps) memcpy(io.steps, hb + L.steps, c * 4);
     if (io.flag) memcpy(io.flag, hb + L.flag, 4);
+    if (io.ids_back) memcpy(io.ids_back, hb + L.ids, c * 4);
     return MK_OK;
 }
 
@@ -4208,6 +4221,161 @@ int promote_launch(mk_session *s, const uint32_t *d_sel, uint64_t first, uint64_
     return MK_OK;
 }
 
+// ---- client keys: the directory of a set (sess_dir.h) -------------------------
+// Waits on the host for everything the set has queued.  Caller holds s->mu.
+int session_quiesce(mk_session *s)
+{
+    if (s->last && s->order && hipEventSynchronize(s->order) != hipSuccess) return MK_EDEVICE;
+    return hipStreamSynchronize(s->stream) == hipSuccess ? MK_OK : MK_EDEVICE;
+}
+
+// Queues the indexed reset's kernel over d_sel[0..m) on `st`; an entry >= n
+// touches nothing.  m in [1, n].
+int reset_sel_launch(mk_session *s, const uint32_t *d_sel, size_t m, hipStream_t st)
+{
+    unsigned blocks;
+    if (!sel_grid(m, &blocks)) return MK_ELIMIT;
+    SessParams p = s->p;
+    SessResetSel q{};
+    if (s->native) q = SessResetSel{s->nsb, s->hand_sb, s->hand_steps, s->hand_call, s->sflags, s->regs, s->slots,
+                                    s->nregs, s->nslots};
+    // the grid's y shares the rows of the tall arrays (stack entries, registers, slots)
+    const uint64_t rows =
+        std::max<uint64_t>({(uint64_t)s->nstack * s->cap, (uint64_t)s->nregs, (uint64_t)s->nslots, (uint64_t)1});
+    uint64_t mm = m;
+    void *args[] = {(void *)&p, (void *)&q, (void *)&d_sel, (void *)&mm};
+    return hipLaunchKernel(reinterpret_cast<void *>(&tis_session_reset_sel),
+                           dim3(blocks, (unsigned)std::min<uint64_t>(rows, 64)), dim3(kBlock), args, 0,
+                           st) == hipSuccess
+               ? MK_OK
+               : MK_EDEVICE;
+}
+
+// Room in a directory scratch, as queue_reserve: growing waits for the set's
+// last launch, a failed allocation leaves the set without that scratch and
+// usable.  Caller holds s->mu and has the device current.
+int dir_reserve(mk_session *s, size_t want, void **buf, size_t *cap, bool bind)
+{
+    if (want <= *cap) return MK_OK;
+    if (int rc = session_quiesce(s)) return rc;
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    const size_t c = std::min<size_t>(std::max<size_t>(want + want / 2, 4096), 0xffffffffull);
+    const size_t bytes = bind ? sd::sd_bind_layout(c, nullptr).bytes : sd::sd_rel_layout(s->n, c, nullptr).bytes;
+    if (hipMalloc(buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *buf = nullptr;
+        return MK_ENOMEM;
+    }
+    *cap = c;
+    if (bind) s->dir->bind_dirty = true; // a fresh scratch table is not an empty one
+    return MK_OK;
+}
+
+// The bind on `st`.  Caller holds s->mu, has the device current, has ordered
+// `st` after the set's last launch and marks it afterwards; s->dir is there,
+// total in [1, 2^32).  Touches no session state.
+int dir_bind_launch(mk_session *s, const uint64_t *d_keys, size_t total, uint32_t *d_ids, uint32_t *d_counts,
+                    hipStream_t st)
+{
+    if (s->broken) return MK_EDEVICE;
+    sd::SdDir *d = s->dir;
+    if (int rc = dir_reserve(s, total, &d->d_bind, &d->bind_cap, true)) return rc;
+    const sd::SdBindBufs q = sd::sd_bind_layout(d->bind_cap, d->d_bind);
+    if (d->bind_dirty) {
+        hipLaunchKernelGGL(sd::sd_clear, dim3(sd::sd_blocks(q.sslots)), dim3(sd::kSdBlock), 0, st, q.skey, q.sfirst,
+                           q.sslots);
+        if (hipGetLastError() != hipSuccess || hipMemsetAsync(d->w + sd::kRejReq, 0, 4, st) != hipSuccess)
+            return MK_EDEVICE;
+        d->bind_dirty = false;
+    }
+    const sd::SdBind b{d_keys, (uint32_t)total, d_ids, q.rslot, q.rank, q.skey, q.sfirst, q.sinst,
+                       (uint32_t)(q.sslots - 1), d->tkey, d->tval, d->slots - 1u, d->owner, d->fifo, (uint32_t)s->n,
+                       d->w};
+    const int rc = sd::sd_bind(b, q.sums, d_counts, st);
+    if (rc) d->bind_dirty = true;
+    return rc;
+}
+
+int dir_lookup_launch(mk_session *s, const uint64_t *d_keys, size_t total, uint32_t *d_ids, hipStream_t st)
+{
+    if (s->broken) return MK_EDEVICE;
+    const sd::SdDir *d = s->dir;
+    hipLaunchKernelGGL(sd::sd_lookup, dim3(sd::sd_blocks(total)), dim3(sd::kSdBlock), 0, st, d_keys, (uint32_t)total,
+                       (const uint64_t *)d->tkey, (const uint32_t *)d->tval, d->slots - 1u, d_ids);
+    return sd::sd_launched();
+}
+
+// The table rebuilt from owner[] on `st`.
+int dir_rebuild_launch(mk_session *s, hipStream_t st)
+{
+    sd::SdDir *d = s->dir;
+    hipLaunchKernelGGL(sd::sd_clear, dim3(sd::sd_blocks(d->slots)), dim3(sd::kSdBlock), 0, st, d->tkey, d->tval,
+                       (uint64_t)d->slots);
+    hipLaunchKernelGGL(sd::sd_rebuild, dim3(sd::sd_blocks(s->n)), dim3(sd::kSdBlock), 0, st,
+                       (const uint64_t *)d->owner, (uint32_t)s->n, d->tkey, d->tval, d->slots - 1u, d->w);
+    d->tomb_bound = 0;
+    return sd::sd_launched();
+}
+
+// The release on `st`, as dir_bind_launch; m in [1, 2^32).  *queued: something
+// that writes session state or the directory may be running.
+int dir_release_launch(mk_session *s, const uint64_t *d_keys, size_t m, uint32_t *d_released, hipStream_t st)
+{
+    if (s->broken) return MK_EDEVICE;
+    sd::SdDir *d = s->dir;
+    if (int rc = dir_reserve(s, m, &d->d_rel, &d->rel_cap, false)) return rc;
+    const sd::SdRelBufs q = sd::sd_rel_layout(s->n, d->rel_cap, d->d_rel);
+    const uint32_t n = (uint32_t)s->n, mm = (uint32_t)m, cap = mm < n ? mm : n;
+    const dim3 grid(sd::sd_blocks(m)), blk(sd::kSdBlock);
+    hipLaunchKernelGGL(sd::sd_rel_find, grid, blk, 0, st, d_keys, mm, (const uint64_t *)d->tkey,
+                       (const uint32_t *)d->tval, d->slots - 1u, d->owner, n, q.rinst, q.rslot);
+    hipLaunchKernelGGL(sd::sd_rel_apply, grid, blk, 0, st, (const uint32_t *)q.rinst, (const uint32_t *)q.rslot, mm,
+                       d->tkey, d->w);
+    if (int rc = sd::sd_launched()) return rc;
+    // The tombstones are queued, whatever fails from here on.  The bound counts
+    // listed keys, not released ones: how many of them were bound is on the device.
+    d->tomb_bound += m;
+    // the released instances distinct and increasing, padded to cap entries
+    if (int rc = rg::rg_group(n, q.rinst, mm, q.perm, q.sel, q.off, q.count, q.tmp, st)) return rc;
+    if (int rc = reset_sel_launch(s, q.sel, cap, st)) return rc;
+    hipLaunchKernelGGL(sd::sd_rel_push, dim3(sd::sd_blocks(cap)), blk, 0, st, (const uint32_t *)q.sel,
+                       (const uint32_t *)q.count, cap, d->fifo, n, (const uint32_t *)d->w);
+    hipLaunchKernelGGL(sd::sd_rel_finish, dim3(1), dim3(64), 0, st, d->w, d_released);
+    if (int rc = sd::sd_launched()) return rc;
+    if (d->tomb_bound > d->slots / 4) return dir_rebuild_launch(s, st);
+    return MK_OK;
+}
+
+// A host form's keys (and nothing else) through the staging: `count` keys up,
+// launch(d_keys, d_words) with room for `count` words behind them when the
+// caller wants words back (d_words is null otherwise), the words and `nw` of the directory's counters from w[first] down, one
+// synchronise.  Caller holds s->mu, has the device current and has ordered
+// s->stream after the set's last launch.
+template <class Launch>
+int dir_round_trip(mk_session *s, const uint64_t *keys, size_t count, uint32_t *words, int first, int nw,
+                   Launch launch)
+{
+    const size_t o_words = Carver::al(count * 8); // room there only when the words are asked for
+    if (int rc = session_stage(s, o_words + (words ? Carver::al(count * 4) : 0))) return rc;
+    char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
+    const hipStream_t st = s->stream;
+    memcpy(hb, keys, count * 8);
+    if (hipMemcpyAsync(b, hb, count * 8, hipMemcpyHostToDevice, st) != hipSuccess) return MK_EDEVICE;
+    int rc = launch((const uint64_t *)b, words ? (uint32_t *)(b + o_words) : nullptr);
+    if (rc == MK_OK && words &&
+        hipMemcpyAsync(hb + o_words, b + o_words, count * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = MK_EDEVICE;
+    if (rc == MK_OK && nw &&
+        hipMemcpyAsync(s->dir->h_w, s->dir->w + first, (size_t)nw * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = MK_EDEVICE;
+    // also after a failure: what was queued reads the staging
+    if (hipStreamSynchronize(st) != hipSuccess && rc == MK_OK) rc = MK_EDEVICE;
+    if (rc == MK_OK && words) memcpy(words, hb + o_words, count * 4);
+    return rc;
+}
+
 // Entries of a host form's staging chunk: at most 64 MiB of rows.
 size_t snap_chunk(uint32_t rows, size_t m) { return std::min<size_t>(m, std::max<size_t>(1, ((size_t)64 << 20) / ((size_t)rows * 4))); }
 
@@ -4459,10 +4627,9 @@ int mk_session_create(mk_net *h, int device, size_t n, const mk_opts *opts, mk_s
     return MK_OK;
 }
 
-int mk_session_reset(mk_session *s)
+// mk_session_reset under s->mu (mk_session_dir_open resets too)
+static int session_reset_locked(mk_session *s)
 {
-    if (!s) return MK_EINVAL;
-    std::lock_guard<std::mutex> lk(s->mu);
     mk::DeviceGuard g(s->device);
     if (int rc = mk::session_wait_last(s, s->stream)) return rc;
     if (hipMemsetAsync(s->d_state, 0, s->state_bytes, s->stream) != hipSuccess) return MK_EDEVICE;
@@ -4471,6 +4638,13 @@ int mk_session_reset(mk_session *s)
     s->broken = false; // every session back to its initial state, none handed off
     s->interp_may_hold = false;
     return MK_OK;
+}
+
+int mk_session_reset(mk_session *s)
+{
+    if (!s) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    return session_reset_locked(s);
 }
 
 int mk_session_compute_seq_device(mk_session *s, const int64_t *d_in, size_t ncalls, int32_t *d_out,
@@ -4858,19 +5032,7 @@ int mk_session_reset_indexed(mk_session *s, const uint32_t *sel, size_t m)
     if (int rc = mk::session_wait_last(s, s->stream)) return rc;
     uint32_t *d_sel;
     if (int rc = mk::session_stage_sel(s, sel, m, nullptr, &d_sel)) return rc;
-    mk::SessParams p = s->p;
-    mk::SessResetSel q{};
-    if (s->native) q = mk::SessResetSel{s->nsb, s->hand_sb, s->hand_steps, s->hand_call, s->sflags, s->regs, s->slots,
-                                        s->nregs, s->nslots};
-    // the grid's y shares the rows of the tall arrays (stack entries, registers, slots)
-    const uint64_t rows =
-        std::max<uint64_t>({(uint64_t)s->nstack * s->cap, (uint64_t)s->nregs, (uint64_t)s->nslots, (uint64_t)1});
-    uint64_t mm = m;
-    void *args[] = {(void *)&p, (void *)&q, (void *)&d_sel, (void *)&mm};
-    if (hipLaunchKernel(reinterpret_cast<void *>(&mk::tis_session_reset_sel),
-                        dim3(blocks, (unsigned)std::min<uint64_t>(rows, 64)), dim3(mk::kBlock), args, 0,
-                        s->stream) != hipSuccess)
-        return MK_EDEVICE;
+    if (int rc = mk::reset_sel_launch(s, d_sel, m, s->stream)) return rc;
     if (hipStreamSynchronize(s->stream) != hipSuccess) return MK_EDEVICE;
     // A broken set (mk_session's `broken`) has sessions left handed off by a
     // launch that failed part way, and the host does not know which: only a
@@ -5062,6 +5224,298 @@ int mk_session_serve_device(mk_session *s, const uint32_t *d_ids, const int64_t 
     }
     return mk::serve_launch(s, d_ids, d_in, total, max_slices, max_rounds, d_out, d_status, d_steps, nullptr, d_left,
                             nullptr, nullptr, st);
+}
+
+// ---- client keys: the directory from 64-bit keys to instances (sess_dir.h) ----
+int mk_session_dir_slots(size_t n, uint32_t *slots)
+{
+    if (!slots || n == 0) return MK_EINVAL;
+    return mk::sd::sd_slots(n, slots) ? MK_OK : MK_ELIMIT;
+}
+
+int mk_session_dir_home(const uint64_t *keys, size_t m, uint32_t slots, uint32_t *home)
+{
+    if (slots == 0 || (slots & (slots - 1u)) || (m && (!keys || !home))) return MK_EINVAL;
+    for (size_t t = 0; t < m; t++) home[t] = mk::sd::sd_home(keys[t], slots - 1u);
+    return MK_OK;
+}
+
+int mk_session_dir_open(mk_session *s)
+{
+    if (!s) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->dir || s->n == 0) return MK_EINVAL;
+    uint32_t slots;
+    if (!mk::sd::sd_slots(s->n, &slots)) return MK_ELIMIT;
+    if (int rc = session_reset_locked(s)) return rc;
+    mk::DeviceGuard g(s->device);
+    mk::sd::SdDir *d = new (std::nothrow) mk::sd::SdDir();
+    if (!d) return MK_ENOMEM;
+    d->slots = slots;
+    const size_t bytes = mk::sd::sd_dir_carve(d, s->n, nullptr);
+    if (hipMalloc(&d->d_base, bytes) != hipSuccess ||
+        hipHostMalloc((void **)&d->h_w, mk::sd::kWords * 4, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        mk::sd::sd_dir_free(d);
+        return MK_ENOMEM;
+    }
+    (void)mk::sd::sd_dir_carve(d, s->n, d->d_base);
+    const dim3 blk(mk::sd::kSdBlock);
+    hipLaunchKernelGGL(mk::sd::sd_clear, dim3(mk::sd::sd_blocks(slots)), blk, 0, s->stream, d->tkey, d->tval,
+                       (uint64_t)slots);
+    hipLaunchKernelGGL(mk::sd::sd_open, dim3(mk::sd::sd_blocks(std::max<size_t>(s->n, mk::sd::kWords))), blk, 0,
+                       s->stream, d->owner, d->fifo, (uint32_t)s->n, d->w);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) {
+        mk::sd::sd_dir_free(d);
+        return MK_EDEVICE;
+    }
+    s->dir = d;
+    return MK_OK;
+}
+
+int mk_session_dir_close(mk_session *s)
+{
+    if (!s) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    mk::DeviceGuard g(s->device);
+    const int rc = mk::session_quiesce(s); // a bind or a release may be in flight
+    mk::sd::sd_dir_free(s->dir);
+    s->dir = nullptr;
+    return rc;
+}
+
+int mk_session_dir_info_get(mk_session *s, mk_session_dir_info *out)
+{
+    if (!s || !out) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    if (hipMemcpyAsync(s->dir->h_w, s->dir->w, mk::sd::kWords * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipStreamSynchronize(s->stream) != hipSuccess)
+        return MK_EDEVICE;
+    const uint32_t *w = s->dir->h_w;
+    *out = mk_session_dir_info{s->dir->slots, w[mk::sd::kLive], w[mk::sd::kFree], w[mk::sd::kTomb]};
+    return MK_OK;
+}
+
+int mk_session_dir_export(mk_session *s, uint64_t *owner)
+{
+    if (!s || !owner) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_quiesce(s)) return rc;
+    return hipMemcpy(owner, s->dir->owner, s->n * 8, hipMemcpyDeviceToHost) == hipSuccess ? MK_OK : MK_EDEVICE;
+}
+
+int mk_session_dir_import(mk_session *s, const uint64_t *owner)
+{
+    if (!s || !owner) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    std::vector<uint64_t> bound;
+    std::vector<uint32_t> fifo;
+    for (size_t i = 0; i < s->n; i++) {
+        if (owner[i] == MK_KEY_NONE) fifo.push_back((uint32_t)i);
+        else bound.push_back(owner[i]);
+    }
+    std::sort(bound.begin(), bound.end());
+    if (std::adjacent_find(bound.begin(), bound.end()) != bound.end()) return MK_EINVAL;
+    uint32_t w[mk::sd::kWords] = {0};
+    w[mk::sd::kFree] = (uint32_t)fifo.size();
+    w[mk::sd::kLive] = (uint32_t)bound.size();
+    mk::sd::SdDir *d = s->dir;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_quiesce(s)) return rc;
+    if (hipMemcpy(d->owner, owner, s->n * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        (!fifo.empty() && hipMemcpy(d->fifo, fifo.data(), fifo.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(d->w, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess)
+        return MK_EDEVICE;
+    if (int rc = mk::dir_rebuild_launch(s, s->stream)) return rc;
+    return hipStreamSynchronize(s->stream) == hipSuccess ? MK_OK : MK_EDEVICE;
+}
+
+int mk_session_bind_device(mk_session *s, const uint64_t *d_keys, size_t total, uint32_t *d_ids, uint32_t *d_counts,
+                           void *stream)
+{
+    if (!s || total > 0xffffffffull || (total && (!d_keys || !d_ids))) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (total == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    hipStream_t st;
+    if (int rc = mk::session_enter(s, stream, &st)) return rc;
+    const int rc = mk::dir_bind_launch(s, d_keys, total, d_ids, d_counts, st);
+    // it wrote the directory: a later launch on another stream waits for it
+    const int mr = mk::session_mark(s, st);
+    return rc ? rc : mr;
+}
+
+int mk_session_bind(mk_session *s, const uint64_t *keys, size_t total, uint32_t *ids, size_t counts[3])
+{
+    if (!s || total > 0xffffffffull || (total && (!keys || !ids))) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (counts) counts[0] = counts[1] = counts[2] = 0;
+    if (total == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    if (int rc = mk::dir_round_trip(s, keys, total, ids, mk::sd::kOut0, 3, [&](const uint64_t *dk, uint32_t *dw) {
+            return mk::dir_bind_launch(s, dk, total, dw, nullptr, s->stream);
+        }))
+        return rc;
+    if (counts)
+        for (int i = 0; i < 3; i++) counts[i] = s->dir->h_w[i];
+    return MK_OK;
+}
+
+int mk_session_lookup_device(mk_session *s, const uint64_t *d_keys, size_t total, uint32_t *d_ids, void *stream)
+{
+    if (!s || total > 0xffffffffull || (total && (!d_keys || !d_ids))) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (total == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    hipStream_t st;
+    if (int rc = mk::session_enter(s, stream, &st)) return rc;
+    const int rc = mk::dir_lookup_launch(s, d_keys, total, d_ids, st);
+    // it read the directory: a later bind or release on another stream waits for it
+    const int mr = mk::session_mark(s, st);
+    return rc ? rc : mr;
+}
+
+int mk_session_lookup(mk_session *s, const uint64_t *keys, size_t total, uint32_t *ids)
+{
+    if (!s || total > 0xffffffffull || (total && (!keys || !ids))) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (total == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    return mk::dir_round_trip(s, keys, total, ids, 0, 0, [&](const uint64_t *dk, uint32_t *dw) {
+        return mk::dir_lookup_launch(s, dk, total, dw, s->stream);
+    });
+}
+
+int mk_session_release_device(mk_session *s, const uint64_t *d_keys, size_t m, uint32_t *d_released, void *stream)
+{
+    if (!s || m > 0xffffffffull || (m && !d_keys)) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (m == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    hipStream_t st;
+    if (int rc = mk::session_enter(s, stream, &st)) return rc;
+    const int rc = mk::dir_release_launch(s, d_keys, m, d_released, st);
+    const int mr = mk::session_mark(s, st);
+    return rc ? rc : mr;
+}
+
+int mk_session_release(mk_session *s, const uint64_t *keys, size_t m, size_t *released)
+{
+    if (!s || m > 0xffffffffull || (m && !keys)) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (released) *released = 0;
+    if (m == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    if (int rc = mk::dir_round_trip(s, keys, m, nullptr, mk::sd::kRelOut, 1, [&](const uint64_t *dk, uint32_t *) {
+            return mk::dir_release_launch(s, dk, m, nullptr, s->stream);
+        }))
+        return rc;
+    if (released) *released = s->dir->h_w[0];
+    return MK_OK;
+}
+
+int mk_session_compute_queue_keyed(mk_session *s, const uint64_t *keys, const int64_t *in, size_t total, int32_t *out,
+                                   uint8_t *status, uint32_t *steps, uint32_t *ids, size_t counts[3])
+{
+    if (!s || total > 0xffffffffull || (total && (!keys || !in || !out || !status))) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (counts) counts[0] = counts[1] = counts[2] = 0;
+    if (total == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    uint32_t busy = 0;
+    mk::HostIO io = mk::HostIO::of(total, in, out, status, steps);
+    io.keys = keys;
+    io.ids_back = ids;
+    io.flag = &busy;
+    mk::sd::SdDir *d = s->dir;
+    int rc = mk::session_round_trip(s, io, [&](const mk::StageDev &v) {
+        if (int r = mk::dir_bind_launch(s, v.keys, total, (uint32_t *)v.ids, nullptr, s->stream)) return r;
+        if (hipMemcpyAsync(d->h_w, d->w + mk::sd::kOut0, 12, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+            return (int)MK_EDEVICE;
+        return mk::queue_launch(s, v.ids, v.in, total, v.out, v.status, v.steps, v.flag, s->stream);
+    });
+    if (rc) return rc;
+    if (counts)
+        for (int i = 0; i < 3; i++) counts[i] = d->h_w[i];
+    return busy ? MK_EBUSY : MK_OK;
+}
+
+int mk_session_serve_keyed(mk_session *s, const uint64_t *keys, const int64_t *in, size_t total, uint32_t max_slices,
+                           int32_t *out, uint8_t *status, uint32_t *steps, uint32_t *ids, size_t counts[3],
+                           size_t *still_open, size_t *rounds)
+{
+    if (!s || max_slices == 0 || total > 0xffffffffull || (total && (!keys || !in || !out || !status)))
+        return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir || s->p.mixed) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    if (counts) counts[0] = counts[1] = counts[2] = 0;
+    if (still_open) *still_open = 0;
+    if (rounds) *rounds = 0;
+    if (total == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    uint32_t busy = 0;
+    size_t open = 0, nr = 0;
+    mk::HostIO io = mk::HostIO::of(total, in, out, status, steps);
+    io.keys = keys;
+    io.ids_back = ids;
+    io.flag = &busy;
+    mk::sd::SdDir *d = s->dir;
+    int rc = mk::session_round_trip(s, io, [&](const mk::StageDev &v) {
+        if (int r = mk::dir_bind_launch(s, v.keys, total, (uint32_t *)v.ids, nullptr, s->stream)) return r;
+        if (hipMemcpyAsync(d->h_w, d->w + mk::sd::kOut0, 12, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+            return (int)MK_EDEVICE;
+        return mk::serve_launch(s, v.ids, v.in, total, max_slices, 0, v.out, v.status, v.steps, v.flag, nullptr, &open,
+                                &nr, s->stream);
+    });
+    if (rc) return rc;
+    if (counts)
+        for (int i = 0; i < 3; i++) counts[i] = d->h_w[i];
+    if (still_open) *still_open = open;
+    if (rounds) *rounds = nr;
+    return busy ? MK_EBUSY : MK_OK;
+}
+
+int mk_session_reset_indexed_device(mk_session *s, const uint32_t *d_sel, size_t m, void *stream)
+{
+    if (!s || m > s->n || (m && !d_sel)) return MK_EINVAL;
+    if (m == 0) return MK_OK;
+    std::lock_guard<std::mutex> lk(s->mu);
+    // The host form mends a broken set when its list names all n sessions; a
+    // list on the device cannot be checked for that, so this form refuses.
+    if (s->broken) return MK_EDEVICE;
+    mk::DeviceGuard g(s->device);
+    hipStream_t st;
+    if (int rc = mk::session_enter(s, stream, &st)) return rc;
+    const int rc = mk::reset_sel_launch(s, d_sel, m, st);
+    const int mr = mk::session_mark(s, st);
+    return rc ? rc : mr;
 }
 
 // ---- snapshots: session records out of a set and back (sess_record.h) --------

@@ -82,6 +82,8 @@ class BatchResult:
     steps: Optional[np.ndarray]  # uint32 retired node-instructions, if requested
     still_open: Optional[int] = None  # SessionSet.drain and serve: calls left open at the slice limit
     rounds: Optional[int] = None  # SessionSet.serve: ragged launches made
+    ids: Optional[np.ndarray] = None  # SessionDirectory: uint32, the instance of each request (0xffffffff: none)
+    counts: Optional[tuple] = None  # SessionDirectory: keys admitted, keys rejected, requests of rejected keys
 
     @property
     def has_output(self) -> np.ndarray:
@@ -715,6 +717,27 @@ class SessionSet:
             return
         N.check(N.lib().mk_session_reset(self._h), "mk_session_reset")
 
+    def reset_device(self, index_ptr, m, stream=None):
+        """:meth:`reset` of the ``m`` instances listed in the device uint32
+        array ``index_ptr`` (strictly increasing, taken on trust; an entry
+        ``>= n`` touches nothing), asynchronous on ``stream``
+        (mk_session_reset_indexed_device)."""
+        if not 0 <= m <= self.n:
+            raise ValueError(f"m = {m} outside [0, {self.n}]")
+        N.check(N.lib().mk_session_reset_indexed_device(self._h, index_ptr, m, stream),
+                "mk_session_reset_indexed_device")
+
+    # ---- client keys (include/mk.h: a directory from 64-bit keys to instances) ----
+    def directory(self) -> "SessionDirectory":
+        """The set's directory from client keys to instances, opened on first
+        use (mk_session_dir_open: that resets the set and frees every
+        instance)."""
+        d = getattr(self, "_dir", None)
+        if d is None:
+            N.check(N.lib().mk_session_dir_open(self._h), "mk_session_dir_open")
+            d = self._dir = SessionDirectory(self)
+        return d
+
     # ---- snapshots (include/mk.h: a session's state out of the set and back) ----
     def layout(self) -> "N.mk_session_layout":
         """What a block of this set's session records looks like (mk_session_layout_get)."""
@@ -840,6 +863,193 @@ class SessionSet:
             self.close()
         except Exception:
             pass
+
+
+KEY_NONE = (1 << 64) - 1  # MK_KEY_NONE: the key that is never bound
+NO_INSTANCE = 0xFFFFFFFF  # the id of a request that touches no instance
+
+
+class SessionDirectory:
+    """The directory of a :class:`SessionSet` from 64-bit client keys to its
+    instances, kept on the GPU with a FIFO of the free instances (include/mk.h,
+    client keys).  A new key takes the instance at the front of the FIFO, which
+    is in the post-/reset state; :meth:`release` resets a departed client's
+    instance and puts it at the back.  Every integer in ``[0, 2^64)`` is a
+    key; :data:`KEY_NONE` marks a request of no client, which is never bound
+    and never served.  From :meth:`SessionSet.directory`."""
+
+    def __init__(self, sset: "SessionSet"):
+        self._set = sset
+
+    @property
+    def _h(self):
+        if getattr(self._set, "_dir", None) is not self:
+            raise ValueError("this directory has been closed")
+        return self._set._h
+
+    @staticmethod
+    def _keys(keys, values=None):
+        """Keys as the C ABI takes them (uint64; with ``values``, int64 of the
+        same length beside them); ValueError names the first offending
+        position."""
+        if isinstance(keys, np.ndarray) and keys.dtype.kind != "O":
+            a = keys.reshape(-1)
+            if a.size and a.dtype.kind not in "iu":
+                raise ValueError(f"keys position 0: {a[0]!r} is not an integer (dtype {a.dtype})")
+            if a.size and a.dtype.kind == "i" and (a < 0).any():
+                t = int(np.argmax(a < 0))
+                raise ValueError(f"keys position {t}: {a[t]} is negative")
+            k = a.astype(np.uint64) if a.size else np.zeros(0, np.uint64)
+        else:
+            each = list(keys.reshape(-1)) if isinstance(keys, np.ndarray) else list(keys)
+            for t, x in enumerate(each):
+                if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                    raise ValueError(f"keys position {t}: {x!r} is not an integer")
+                if x < 0:
+                    raise ValueError(f"keys position {t}: {x} is negative")
+                if x >= 1 << 64:
+                    raise ValueError(f"keys position {t}: {x} is 2^64 or more")
+            k = np.array([int(x) for x in each], dtype=np.uint64)
+        if k.size >= 1 << 32:
+            raise ValueError(f"keys position {(1 << 32) - 1}: 2^32 keys or more")
+        k = np.ascontiguousarray(k)
+        if values is None:
+            return k
+        v = np.asarray(values, dtype=np.int64).reshape(-1)
+        if v.size != k.size:
+            t = min(v.size, k.size)
+            raise ValueError(f"keys position {t}: {k.size} keys for {v.size} values (len(keys) != len(values))")
+        return k, np.ascontiguousarray(v)
+
+    def bind(self, keys):
+        """The instance of every key, in arrival order, new keys admitted
+        (mk_session_bind): ``(ids, counts)`` -- uint32 ids, 0xffffffff for
+        :data:`KEY_NONE` and for a key rejected because no instance was free,
+        and ``counts = (keys admitted, keys rejected, requests of rejected
+        keys)``.  New keys take the free instances in the order of their first
+        occurrence."""
+        k = self._keys(keys)
+        ids = np.zeros(k.size, np.uint32)
+        c = (C.c_size_t * 3)()
+        N.check(N.lib().mk_session_bind(self._h, _ptr(k), k.size, _ptr(ids), c), "mk_session_bind")
+        return ids, tuple(int(x) for x in c)
+
+    def lookup(self, keys) -> np.ndarray:
+        """As :meth:`bind`, but nothing is admitted: an unbound key gives
+        0xffffffff (mk_session_lookup)."""
+        k = self._keys(keys)
+        ids = np.zeros(k.size, np.uint32)
+        N.check(N.lib().mk_session_lookup(self._h, _ptr(k), k.size, _ptr(ids)), "mk_session_lookup")
+        return ids
+
+    def release(self, keys) -> int:
+        """Unbind the listed keys, reset their instances and put them at the
+        back of the FIFO in increasing order; the number released
+        (mk_session_release).  Unbound keys and repeats are ignored."""
+        k = self._keys(keys)
+        r = C.c_size_t()
+        N.check(N.lib().mk_session_release(self._h, _ptr(k), k.size, C.byref(r)), "mk_session_release")
+        return r.value
+
+    def compute_queue(self, keys, values, *, steps=True, busy_ok=False) -> BatchResult:
+        """:meth:`bind`, then :meth:`SessionSet.compute_queue` on the ids, in
+        one call with the keys staged once (mk_session_compute_queue_keyed).
+        The result also carries ``ids`` and ``counts``; the requests of
+        rejected keys and of :data:`KEY_NONE` report 0 / 0 / 0."""
+        k, v = self._keys(keys, values)
+        ids = np.zeros(k.size, np.uint32)
+        c = (C.c_size_t * 3)()
+        r = SessionSet._call(self, "mk_session_compute_queue_keyed", k.size, steps, busy_ok, _ptr(k), _ptr(v), k.size,
+                             tail=(_ptr(ids), c))
+        r.ids, r.counts = ids, tuple(int(x) for x in c)
+        return r
+
+    def serve(self, keys, values, *, max_slices=16, steps=True, busy_ok=False, promote=False) -> BatchResult:
+        """:meth:`bind`, then :meth:`SessionSet.serve` on the ids
+        (mk_session_serve_keyed); the result also carries ``ids`` and
+        ``counts``."""
+        n = SessionSet._slices("max_slices", max_slices)
+        k, v = self._keys(keys, values)
+        ids = np.zeros(k.size, np.uint32)
+        c = (C.c_size_t * 3)()
+        left, rounds = C.c_size_t(), C.c_size_t()
+        r = SessionSet._call(self, "mk_session_serve_keyed", k.size, steps, busy_ok, _ptr(k), _ptr(v), k.size, n,
+                             tail=(_ptr(ids), c, C.byref(left), C.byref(rounds)))
+        r.ids, r.counts = ids, tuple(int(x) for x in c)
+        r.still_open, r.rounds = left.value, rounds.value
+        if promote:
+            self._set.promote()
+        return r
+
+    def export(self) -> np.ndarray:
+        """The key of every instance (uint64, :data:`KEY_NONE` for a free one)."""
+        owner = np.zeros(self._set.n, np.uint64)
+        N.check(N.lib().mk_session_dir_export(self._h, _ptr(owner)), "mk_session_dir_export")
+        return owner
+
+    def load(self, owner):
+        """Replace the whole directory by an array as :meth:`export` gives it;
+        no instance is reset, and the free instances queue up in increasing
+        order.  ValueError, with nothing changed, when a key occurs twice."""
+        o = self._keys(owner)
+        if o.size != self._set.n:
+            raise ValueError(f"owner position {min(o.size, self._set.n)}: {o.size} keys for {self._set.n} instances")
+        rc = N.lib().mk_session_dir_import(self._h, _ptr(o))
+        if rc == N.MK_EINVAL:
+            raise ValueError("a key occurs twice: nothing loaded")
+        N.check(rc, "mk_session_dir_import")
+
+    def info(self) -> "N.mk_session_dir_info":
+        """``slots``, ``live``, ``free`` and ``tombstones`` of the directory."""
+        i = N.mk_session_dir_info()
+        N.check(N.lib().mk_session_dir_info_get(self._h, C.byref(i)), "mk_session_dir_info_get")
+        return i
+
+    def close(self):
+        """Drop the directory; the instances stay as they are."""
+        if getattr(self._set, "_dir", None) is self:
+            N.check(N.lib().mk_session_dir_close(self._set._h), "mk_session_dir_close")
+            self._set._dir = None
+
+    @staticmethod
+    def _total(total):
+        if not 0 <= total < 1 << 32:
+            raise ValueError(f"total = {total} outside [0, 2^32)")
+        return total
+
+    def bind_device(self, keys_ptr, total, ids_ptr, counts_ptr=None, *, stream=None):
+        """:meth:`bind` on device arrays (uint64 keys, uint32 ids, three uint32
+        counts or None), asynchronous on ``stream`` and without any read-back
+        (mk_session_bind_device).  The ids feed
+        :meth:`SessionSet.compute_queue_device` and ``serve_device`` as they are."""
+        N.check(N.lib().mk_session_bind_device(self._h, keys_ptr, self._total(total), ids_ptr, counts_ptr, stream),
+                "mk_session_bind_device")
+
+    def lookup_device(self, keys_ptr, total, ids_ptr, *, stream=None):
+        """:meth:`lookup` on device arrays, asynchronous on ``stream``."""
+        N.check(N.lib().mk_session_lookup_device(self._h, keys_ptr, self._total(total), ids_ptr, stream),
+                "mk_session_lookup_device")
+
+    def release_device(self, keys_ptr, m, released_ptr=None, *, stream=None):
+        """:meth:`release` of ``m`` device keys, asynchronous on ``stream``;
+        ``released_ptr`` (one device uint32, or None) takes the number released."""
+        N.check(N.lib().mk_session_release_device(self._h, keys_ptr, self._total(m), released_ptr, stream),
+                "mk_session_release_device")
+
+
+def directory_slots(n) -> int:
+    """The table size of a directory for ``n`` instances (mk_session_dir_slots)."""
+    s = C.c_uint32()
+    N.check(N.lib().mk_session_dir_slots(n, C.byref(s)), "mk_session_dir_slots")
+    return s.value
+
+
+def directory_home(keys, slots) -> np.ndarray:
+    """Where each key's probe starts in a table of ``slots`` slots (mk_session_dir_home)."""
+    k = SessionDirectory._keys(keys)
+    home = np.zeros(k.size, np.uint32)
+    N.check(N.lib().mk_session_dir_home(_ptr(k), k.size, slots, _ptr(home)), "mk_session_dir_home")
+    return home
 
 
 class SessionSnapshot:
