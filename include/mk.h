@@ -599,6 +599,87 @@ int mk_session_serve_keyed(mk_session *s, const uint64_t *keys, const int64_t *i
                            uint32_t *ids /* nullable */, size_t counts[3] /* nullable */,
                            size_t *still_open /* nullable */, size_t *rounds /* nullable */);
 
+/* ---- idle clients: use stamps, selection and eviction ------------------------
+ * A full directory rejects new keys.  A tracked one knows when each client was
+ * last seen, so that the clients silent longest can make room, or be parked on
+ * the host (snapshot, then release) before they have to.
+ *
+ *   track    turns tracking on: a 64-bit use stamp per instance on the device
+ *            and a 64-bit clock on the host, the number of binds queued since
+ *            (a bind of total == 0 launches nothing and does not tick).  Every
+ *            instance bound at that moment gets stamp 0.  From then on every
+ *            bind (mk_session_bind, _device, the keyed forms, bind_evict)
+ *            stamps every instance its requests resolve to, hits and admissions
+ *            alike, with the clock after its tick.  Lookup and release stamp
+ *            nothing; mk_session_dir_import stamps every instance it binds with
+ *            the current clock.  An untracked directory runs the same kernels,
+ *            which skip the store.
+ *   age(i)   min(clock - stamp[i], 2^32 - 1)
+ *   eligible instance i for min_idle: bound, age(i) >= max(min_idle, 1), and no
+ *            call open.
+ *   the k most idle: the first k of the eligible instances ordered by (age
+ *            descending, instance ascending).  Every list of victims is
+ *            reported in increasing instance order, min(want, n) entries (for
+ *            bind_evict min(max_evict, n)), padded with MK_KEY_NONE /
+ *            0xffffffff: a valid list for the indexed, snapshot and reset
+ *            forms.  Nothing depends on the order in which the GPU's threads run.
+ *   idle_select  reports the min(want, eligible) most idle: keys, instances and
+ *            their number.  Changes nothing and ticks nothing.
+ *   evict    the same selection, then the victims are released as
+ *            mk_session_release releases them (reset, to the back of the FIFO
+ *            in increasing order).  keys and ids are nullable.
+ *   bind_evict  a bind that makes room: need = max(0, new keys - free), and the
+ *            k = min(need, max_evict, eligible) most idle are evicted before
+ *            the new keys are admitted -- from the instances that were free
+ *            first, then from the victims in increasing order.  What this bind's
+ *            requests resolve to has age 0 and is never evicted.  What still
+ *            finds no instance is rejected as by bind.  counts = {admitted,
+ *            rejected keys, requests of rejected keys, evicted}.  With
+ *            max_evict == 0 it is mk_session_bind in every output.
+ *   use_export  stamp[i] (0 for a free instance) and the clock; use_import
+ *            replaces both, beside mk_session_dir_export / _import (import the
+ *            directory first).  MK_EINVAL, and nothing changes, when a bound
+ *            instance has a stamp above the clock.
+ *
+ * A selection passes over the n instances a few times (sess_evict.h); a
+ * bind_evict that lacks nothing pays the launches only.  The host cannot know
+ * how many an eviction evicted on the device, so its bound on the tombstones
+ * grows by min(want, n) (min(max_evict, n)) per evicting call, and the table is
+ * rebuilt behind the call that takes the bound past slots / 4:
+ * info.tombstones <= info.slots / 4 holds after every call.  Ask for no more
+ * evictions than a call may need.
+ *
+ * MK_EINVAL on an untracked directory (track: without a directory and on a
+ * second call), for null required arrays and for want or max_evict >= 2^32;
+ * want == 0 is MK_OK and launches nothing.  Ordering, host and device forms as
+ * for the directory above. */
+typedef struct {
+    uint64_t clock;    /* binds queued since tracking began */
+    uint32_t tracking; /* 1 when mk_session_dir_track has been called */
+    uint32_t reserved;
+} mk_session_dir_use_info;
+
+int mk_session_dir_track(mk_session *s); /* undone by mk_session_dir_close */
+int mk_session_dir_use_info_get(mk_session *s, mk_session_dir_use_info *out);
+int mk_session_dir_use_export(mk_session *s, uint64_t *last /* n */, uint64_t *clock /* nullable */);
+int mk_session_dir_use_import(mk_session *s, const uint64_t *last /* n */, uint64_t clock);
+
+int mk_session_idle_select(mk_session *s, size_t want, uint32_t min_idle, uint64_t *keys, uint32_t *ids,
+                           size_t *count /* nullable */);
+int mk_session_idle_select_device(mk_session *s, size_t want, uint32_t min_idle, uint64_t *d_keys, uint32_t *d_ids,
+                                  uint32_t *d_count /* nullable */, void *stream);
+int mk_session_evict(mk_session *s, size_t want, uint32_t min_idle, uint64_t *keys /* nullable */,
+                     uint32_t *ids /* nullable */, size_t *count /* nullable */);
+int mk_session_evict_device(mk_session *s, size_t want, uint32_t min_idle, uint64_t *d_keys /* nullable */,
+                            uint32_t *d_ids /* nullable */, uint32_t *d_count /* nullable */, void *stream);
+int mk_session_bind_evict(mk_session *s, const uint64_t *keys, size_t total, uint32_t *ids, size_t max_evict,
+                          uint32_t min_idle, uint64_t *ev_keys /* nullable */, uint32_t *ev_ids /* nullable */,
+                          size_t counts[4] /* nullable */);
+int mk_session_bind_evict_device(mk_session *s, const uint64_t *d_keys, size_t total, uint32_t *d_ids,
+                                 size_t max_evict, uint32_t min_idle, uint64_t *d_ev_keys /* nullable */,
+                                 uint32_t *d_ev_ids /* nullable */, uint32_t *d_counts /* nullable, 4 words */,
+                                 void *stream);
+
 /* The device form of mk_session_reset_indexed, asynchronous on `stream`: d_sel
  * is taken ON TRUST (strictly increasing); an entry >= n touches nothing.
  * MK_EDEVICE on a set broken by a failed launch: only the host forms, which can

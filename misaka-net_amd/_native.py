@@ -104,6 +104,10 @@ class mk_session_dir_info(C.Structure):
     _fields_ = [("slots", C.c_uint32), ("live", C.c_uint32), ("free", C.c_uint32), ("tombstones", C.c_uint32)]
 
 
+class mk_session_dir_use_info(C.Structure):
+    _fields_ = [("clock", C.c_uint64), ("tracking", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 MK_KEY_NONE = (1 << 64) - 1
 
 # name -> (restype, argtypes); every symbol include/mk.h declares.
@@ -195,6 +199,24 @@ SIGNATURES = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                   C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "mk_session_reset_indexed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mk_session_dir_track": (C.c_int, [C.c_void_p]),
+    "mk_session_dir_use_info_get": (C.c_int, [C.c_void_p, C.POINTER(mk_session_dir_use_info)]),
+    "mk_session_dir_use_export": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mk_session_dir_use_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mk_session_idle_select": (
+        C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "mk_session_idle_select_device": (
+        C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_evict": (
+        C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "mk_session_evict_device": (
+        C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mk_session_bind_evict": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
+                  C.c_void_p]),
+    "mk_session_bind_evict_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p]),
     "mk_session_dir_slots": (C.c_int, [C.c_size_t, C.POINTER(C.c_uint32)]),
     "mk_session_dir_home": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "mk_session_layout_get": (C.c_int, [C.c_void_p, C.POINTER(mk_session_layout)]),

@@ -3092,6 +3092,7 @@ void *pick_session_kernel(int nprog, bool sel = false)
 #include "sess_drain.h"
 #include "sess_serve.h"
 #include "sess_dir.h"
+#include "sess_evict.h"
 
 struct mk_session {
     mk_net *h = nullptr;
@@ -4276,8 +4277,42 @@ int dir_reserve(mk_session *s, size_t want, void **buf, size_t *cap, bool bind)
 // The bind on `st`.  Caller holds s->mu, has the device current, has ordered
 // `st` after the set's last launch and marks it afterwards; s->dir is there,
 // total in [1, 2^32).  Touches no session state.
+int dir_rebuild_launch(mk_session *s, hipStream_t st);
+
+// What a selection hands out: the victims' keys and instances (device,
+// `cap` entries each, nullable) and their number (one word, nullable).
+struct EvOut {
+    uint32_t cap; // the most to select, in [1, n]
+    uint32_t min_idle;
+    uint64_t *d_keys;
+    uint32_t *d_ids;
+    uint32_t *d_count;
+};
+
+// The k most idle of a tracked directory on `st`, as dir_bind_launch; with
+// `release` they are evicted.  from_bind: between the halves of a bind, k is
+// what that bind lacks.  The caller queues the rebuild the bound asks for.
+int dir_select_launch(mk_session *s, const EvOut &e, bool from_bind, bool release, hipStream_t st)
+{
+    sd::SdDir *d = s->dir;
+    const uint32_t n = (uint32_t)s->n;
+    const ev::EvBufs q = ev::ev_layout(s->n, d->d_ev);
+    const ev::EvSrc src{d->owner, d->last, s->p.io, n, d->clock, e.min_idle ? e.min_idle : 1u};
+    if (int rc = ev::ev_select(src, q, e.cap, from_bind, e.d_ids, e.d_keys, d->w, e.d_count, st)) return rc;
+    if (!release) return MK_OK;
+    hipLaunchKernelGGL(ev::ev_release, dim3(sd::sd_blocks(e.cap)), dim3(sd::kSdBlock), 0, st, (const uint32_t *)q.ctl,
+                       (const uint32_t *)q.sel, e.cap, d->tkey, (const uint32_t *)d->tval, d->slots - 1u, d->owner,
+                       d->fifo, n, (const uint32_t *)d->w);
+    if (int rc = sd::sd_launched()) return rc;
+    // How many were evicted is on the device: the bound takes the most there can be.
+    d->tomb_bound += e.cap;
+    if (int rc = reset_sel_launch(s, q.sel, e.cap, st)) return rc;
+    hipLaunchKernelGGL(ev::ev_finish, dim3(1), dim3(64), 0, st, (const uint32_t *)q.ctl, d->w);
+    return sd::sd_launched();
+}
+
 int dir_bind_launch(mk_session *s, const uint64_t *d_keys, size_t total, uint32_t *d_ids, uint32_t *d_counts,
-                    hipStream_t st)
+                    hipStream_t st, const EvOut *evict = nullptr)
 {
     if (s->broken) return MK_EDEVICE;
     sd::SdDir *d = s->dir;
@@ -4292,9 +4327,13 @@ int dir_bind_launch(mk_session *s, const uint64_t *d_keys, size_t total, uint32_
     }
     const sd::SdBind b{d_keys, (uint32_t)total, d_ids, q.rslot, q.rank, q.skey, q.sfirst, q.sinst,
                        (uint32_t)(q.sslots - 1), d->tkey, d->tval, d->slots - 1u, d->owner, d->fifo, (uint32_t)s->n,
-                       d->w};
-    const int rc = sd::sd_bind(b, q.sums, d_counts, st);
+                       d->w, d->last, d->last ? ++d->clock : 0};
+    int rc = sd::sd_bind_front(b, q.sums, st);
+    // the hits are stamped by now: what this bind touches has age 0
+    if (rc == MK_OK && evict) rc = dir_select_launch(s, *evict, true, true, st);
+    if (rc == MK_OK) rc = sd::sd_bind_back(b, d_counts, st);
     if (rc) d->bind_dirty = true;
+    if (rc == MK_OK && evict && d->tomb_bound > d->slots / 4) rc = dir_rebuild_launch(s, st);
     return rc;
 }
 
@@ -4374,6 +4413,44 @@ int dir_round_trip(mk_session *s, const uint64_t *keys, size_t count, uint32_t *
     if (hipStreamSynchronize(st) != hipSuccess && rc == MK_OK) rc = MK_EDEVICE;
     if (rc == MK_OK && words) memcpy(words, hb + o_words, count * 4);
     return rc;
+}
+
+// dir_round_trip for the forms that select: `count` keys up and their ids back
+// (a bind; count 0 otherwise), and room for the victims' lists of `cap`
+// entries, each copied back when the caller gave the array.
+template <class Launch>
+int dir_evict_round_trip(mk_session *s, const uint64_t *keys, size_t count, uint32_t *ids, size_t cap,
+                         uint64_t *ev_keys, uint32_t *ev_ids, int first, int nw, Launch launch)
+{
+    Carver k;
+    const size_t o_keys = k.skip(count * 8), o_ids = k.skip(count * 4), o_evk = k.skip(ev_keys ? cap * 8 : 0),
+                 o_evi = k.skip(ev_ids ? cap * 4 : 0);
+    if (int rc = session_stage(s, k.at ? k.at : 256)) return rc;
+    char *b = (char *)s->d_stage, *hb = (char *)s->h_stage;
+    const hipStream_t st = s->stream;
+    if (count) {
+        memcpy(hb + o_keys, keys, count * 8);
+        if (hipMemcpyAsync(b + o_keys, hb + o_keys, count * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+            return MK_EDEVICE;
+    }
+    auto down = [&](size_t at, size_t bytes) {
+        return hipMemcpyAsync(hb + at, b + at, bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+    };
+    int rc = launch((const uint64_t *)(b + o_keys), (uint32_t *)(b + o_ids), ev_keys ? (uint64_t *)(b + o_evk) : nullptr,
+                    ev_ids ? (uint32_t *)(b + o_evi) : nullptr);
+    if (rc == MK_OK && ((count && !down(o_ids, count * 4)) || (ev_keys && !down(o_evk, cap * 8)) ||
+                        (ev_ids && !down(o_evi, cap * 4))))
+        rc = MK_EDEVICE;
+    if (rc == MK_OK && nw &&
+        hipMemcpyAsync(s->dir->h_w, s->dir->w + first, (size_t)nw * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = MK_EDEVICE;
+    // also after a failure: what was queued reads the staging
+    if (hipStreamSynchronize(st) != hipSuccess && rc == MK_OK) rc = MK_EDEVICE;
+    if (rc) return rc;
+    if (count) memcpy(ids, hb + o_ids, count * 4);
+    if (ev_keys) memcpy(ev_keys, hb + o_evk, cap * 8);
+    if (ev_ids) memcpy(ev_ids, hb + o_evi, cap * 4);
+    return MK_OK;
 }
 
 // Entries of a host form's staging chunk: at most 64 MiB of rows.
@@ -5334,7 +5411,208 @@ int mk_session_dir_import(mk_session *s, const uint64_t *owner)
         hipMemcpy(d->w, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess)
         return MK_EDEVICE;
     if (int rc = mk::dir_rebuild_launch(s, s->stream)) return rc;
+    if (d->last) { // a tracked directory: every client it now holds was seen just now
+        hipLaunchKernelGGL(mk::ev::ev_stamp_bound, dim3(mk::ev::ev_layout(s->n, nullptr).grid), dim3(mk::sd::kSdBlock),
+                           0, s->stream, (const uint64_t *)d->owner, d->last, (uint32_t)s->n, d->clock);
+        if (hipGetLastError() != hipSuccess) return MK_EDEVICE;
+    }
     return hipStreamSynchronize(s->stream) == hipSuccess ? MK_OK : MK_EDEVICE;
+}
+
+// ---- use stamps, idle clients and eviction (sess_evict.h) ------------------------
+int mk_session_dir_track(mk_session *s)
+{
+    if (!s) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::sd::SdDir *d = s->dir;
+    if (!d || d->last) return MK_EINVAL;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_quiesce(s)) return rc;
+    const mk::ev::EvBufs L = mk::ev::ev_layout(s->n, nullptr);
+    if (hipMalloc(&d->d_ev, L.bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        d->d_ev = nullptr;
+        return MK_ENOMEM;
+    }
+    uint64_t *last = mk::ev::ev_layout(s->n, d->d_ev).last;
+    hipLaunchKernelGGL(mk::ev::ev_stamp_bound, dim3(L.grid), dim3(mk::sd::kSdBlock), 0, s->stream,
+                       (const uint64_t *)d->owner, last, (uint32_t)s->n, (uint64_t)0);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) {
+        (void)hipFree(d->d_ev);
+        d->d_ev = nullptr;
+        return MK_EDEVICE;
+    }
+    d->last = last;
+    d->clock = 0;
+    return MK_OK;
+}
+
+int mk_session_dir_use_info_get(mk_session *s, mk_session_dir_use_info *out)
+{
+    if (!s || !out) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dir) return MK_EINVAL;
+    *out = mk_session_dir_use_info{s->dir->clock, s->dir->last ? 1u : 0u, 0u};
+    return MK_OK;
+}
+
+int mk_session_dir_use_export(mk_session *s, uint64_t *last, uint64_t *clock)
+{
+    if (!s || !last) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::sd::SdDir *d = s->dir;
+    if (!d || !d->last) return MK_EINVAL;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_quiesce(s)) return rc;
+    std::vector<uint64_t> owner(s->n);
+    if (hipMemcpy(owner.data(), d->owner, s->n * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(last, d->last, s->n * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return MK_EDEVICE;
+    for (size_t i = 0; i < s->n; i++)
+        if (owner[i] == MK_KEY_NONE) last[i] = 0;
+    if (clock) *clock = d->clock;
+    return MK_OK;
+}
+
+int mk_session_dir_use_import(mk_session *s, const uint64_t *last, uint64_t clock)
+{
+    if (!s || !last) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    mk::sd::SdDir *d = s->dir;
+    if (!d || !d->last) return MK_EINVAL;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_quiesce(s)) return rc;
+    std::vector<uint64_t> owner(s->n), v(s->n);
+    if (hipMemcpy(owner.data(), d->owner, s->n * 8, hipMemcpyDeviceToHost) != hipSuccess) return MK_EDEVICE;
+    for (size_t i = 0; i < s->n; i++) {
+        const bool bound = owner[i] != MK_KEY_NONE;
+        if (bound && last[i] > clock) return MK_EINVAL;
+        v[i] = bound ? last[i] : 0;
+    }
+    if (hipMemcpy(d->last, v.data(), s->n * 8, hipMemcpyHostToDevice) != hipSuccess) return MK_EDEVICE;
+    d->clock = clock;
+    return MK_OK;
+}
+
+// The checks the selecting forms share; *cap = min(want, n).
+static int ev_enter(mk_session *s, size_t want, uint32_t *cap)
+{
+    if (!s->dir || !s->dir->last || want > 0xffffffffull) return MK_EINVAL;
+    if (s->broken) return MK_EDEVICE;
+    *cap = (uint32_t)std::min<size_t>(want, s->n);
+    return MK_OK;
+}
+
+static int ev_select_device(mk_session *s, bool release, size_t want, uint32_t min_idle, uint64_t *d_keys,
+                            uint32_t *d_ids, uint32_t *d_count, void *stream)
+{
+    if (!s) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    uint32_t cap;
+    if (int rc = ev_enter(s, want, &cap)) return rc;
+    if (cap == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    hipStream_t st;
+    if (int rc = mk::session_enter(s, stream, &st)) return rc;
+    int rc = mk::dir_select_launch(s, mk::EvOut{cap, min_idle, d_keys, d_ids, d_count}, false, release, st);
+    if (rc == MK_OK && release && s->dir->tomb_bound > s->dir->slots / 4) rc = mk::dir_rebuild_launch(s, st);
+    const int mr = mk::session_mark(s, st);
+    return rc ? rc : mr;
+}
+
+static int ev_select_host(mk_session *s, bool release, size_t want, uint32_t min_idle, uint64_t *keys, uint32_t *ids,
+                          size_t *count)
+{
+    if (!s) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    uint32_t cap;
+    if (int rc = ev_enter(s, want, &cap)) return rc;
+    if (count) *count = 0;
+    if (cap == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    if (int rc = mk::dir_evict_round_trip(
+            s, nullptr, 0, nullptr, cap, keys, ids, mk::sd::kEvOut, 1,
+            [&](const uint64_t *, uint32_t *, uint64_t *dk, uint32_t *di) {
+                int r = mk::dir_select_launch(s, mk::EvOut{cap, min_idle, dk, di, nullptr}, false, release, s->stream);
+                if (r == MK_OK && release && s->dir->tomb_bound > s->dir->slots / 4)
+                    r = mk::dir_rebuild_launch(s, s->stream);
+                return r;
+            }))
+        return rc;
+    if (count) *count = s->dir->h_w[0];
+    return MK_OK;
+}
+
+int mk_session_idle_select(mk_session *s, size_t want, uint32_t min_idle, uint64_t *keys, uint32_t *ids, size_t *count)
+{
+    if (want && (!keys || !ids)) return MK_EINVAL;
+    return ev_select_host(s, false, want, min_idle, keys, ids, count);
+}
+
+int mk_session_idle_select_device(mk_session *s, size_t want, uint32_t min_idle, uint64_t *d_keys, uint32_t *d_ids,
+                                  uint32_t *d_count, void *stream)
+{
+    if (want && (!d_keys || !d_ids)) return MK_EINVAL;
+    return ev_select_device(s, false, want, min_idle, d_keys, d_ids, d_count, stream);
+}
+
+int mk_session_evict(mk_session *s, size_t want, uint32_t min_idle, uint64_t *keys, uint32_t *ids, size_t *count)
+{
+    return ev_select_host(s, true, want, min_idle, keys, ids, count);
+}
+
+int mk_session_evict_device(mk_session *s, size_t want, uint32_t min_idle, uint64_t *d_keys, uint32_t *d_ids,
+                            uint32_t *d_count, void *stream)
+{
+    return ev_select_device(s, true, want, min_idle, d_keys, d_ids, d_count, stream);
+}
+
+int mk_session_bind_evict_device(mk_session *s, const uint64_t *d_keys, size_t total, uint32_t *d_ids, size_t max_evict,
+                                 uint32_t min_idle, uint64_t *d_ev_keys, uint32_t *d_ev_ids, uint32_t *d_counts,
+                                 void *stream)
+{
+    if (!s || total > 0xffffffffull || (total && (!d_keys || !d_ids))) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    uint32_t cap;
+    if (int rc = ev_enter(s, max_evict, &cap)) return rc;
+    if (total == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    hipStream_t st;
+    if (int rc = mk::session_enter(s, stream, &st)) return rc;
+    const mk::EvOut e{cap, min_idle, d_ev_keys, d_ev_ids, d_counts ? d_counts + 3 : nullptr};
+    int rc = MK_OK;
+    if (cap == 0 && d_counts && hipMemsetAsync(d_counts + 3, 0, 4, st) != hipSuccess) rc = MK_EDEVICE;
+    if (rc == MK_OK) rc = mk::dir_bind_launch(s, d_keys, total, d_ids, d_counts, st, cap ? &e : nullptr);
+    const int mr = mk::session_mark(s, st);
+    return rc ? rc : mr;
+}
+
+int mk_session_bind_evict(mk_session *s, const uint64_t *keys, size_t total, uint32_t *ids, size_t max_evict,
+                          uint32_t min_idle, uint64_t *ev_keys, uint32_t *ev_ids, size_t counts[4])
+{
+    if (!s || total > 0xffffffffull || (total && (!keys || !ids))) return MK_EINVAL;
+    std::lock_guard<std::mutex> lk(s->mu);
+    uint32_t cap;
+    if (int rc = ev_enter(s, max_evict, &cap)) return rc;
+    if (counts) counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (total == 0) return MK_OK;
+    mk::DeviceGuard g(s->device);
+    if (int rc = mk::session_wait_last(s, s->stream)) return rc;
+    // the words from kOut0 to kEvOut: the bind's three counts, two of a release's, the evicted
+    const int nw = mk::sd::kEvOut - mk::sd::kOut0 + 1;
+    if (int rc = mk::dir_evict_round_trip(
+            s, keys, total, ids, cap, cap ? ev_keys : nullptr, cap ? ev_ids : nullptr, mk::sd::kOut0, nw,
+            [&](const uint64_t *dk, uint32_t *di, uint64_t *evk, uint32_t *evi) {
+                const mk::EvOut e{cap, min_idle, evk, evi, nullptr};
+                return mk::dir_bind_launch(s, dk, total, di, nullptr, s->stream, cap ? &e : nullptr);
+            }))
+        return rc;
+    if (counts) {
+        for (int i = 0; i < 3; i++) counts[i] = s->dir->h_w[i];
+        counts[3] = cap ? s->dir->h_w[nw - 1] : 0;
+    }
+    return MK_OK;
 }
 
 int mk_session_bind_device(mk_session *s, const uint64_t *d_keys, size_t total, uint32_t *d_ids, uint32_t *d_counts,

@@ -45,6 +45,11 @@
 // three quarters of the slots are ever in use and the rebuilds cost a constant
 // per listed key.
 //
+// A tracked directory (mk_session_dir_track, sess_evict.h) also has last[n],
+// the use stamps: sd_bind_find stores the bind's clock value for every hit and
+// sd_bind_assign for every admission, the kernels that hold the instance
+// anyway.  An untracked one passes a null `last` and the stores are skipped.
+//
 // Every kernel writes with ordinary vector stores and atomics.  Included by
 // mk_exec.hip after req_group.h; everything here is static to it.
 #pragma once
@@ -71,6 +76,7 @@ enum : int {
     kOut2,
     kRel,      // a release: instances released; zero between releases
     kRelOut,   // the last release's count
+    kEvOut,    // the last selection's count (sess_evict.h)
     kWords = 16
 };
 
@@ -210,6 +216,8 @@ struct SdBind {
     const uint32_t *fifo;
     uint32_t n;
     uint32_t *w;
+    uint64_t *last; // a tracked directory's use stamps (sess_evict.h), or null
+    uint64_t now;   // what this bind stamps
 };
 
 // request j is one of a new key: not bound (sd_bind_find left kNoId) and not "no key"
@@ -223,6 +231,8 @@ __global__ void __launch_bounds__(kSdBlock) sd_bind_find(SdBind b)
     uint32_t id = kNoId, slot;
     if (k != kNone) {
         id = sd_find(b.tkey, b.tval, b.mask, k, &slot);
+        // several requests of one key store the same value
+        if (id < b.n && b.last) b.last[id] = b.now;
         if (id == kNoId) {
             // more slots than requests: the claim finds one
             (void)sd_claim(b.skey, b.smask, k, &slot);
@@ -262,6 +272,7 @@ __global__ void __launch_bounds__(kSdBlock) sd_bind_assign(SdBind b)
                     tomb = b.tval[slot] != kEmpty;
                     b.tval[slot] = inst;
                     b.owner[inst] = k;
+                    if (b.last) b.last[inst] = b.now;
                 }
             }
             b.sinst[rs] = inst;
@@ -340,14 +351,21 @@ inline SdBindBufs sd_bind_layout(size_t cap, void *base)
 }
 
 // The kernels of a bind on `st`; b complete, total in [1, 2^32).  The scratch
-// table must be empty, and is again when all of this has run.
-inline int sd_bind(const SdBind &b, uint32_t *sums, uint32_t *d_counts, hipStream_t st)
+// table must be empty, and is again when all of this has run.  In two halves:
+// after the first w[kNew] is known on the device, and a bind that makes room
+// (sess_evict.h) frees instances between them.
+inline int sd_bind_front(const SdBind &b, uint32_t *sums, hipStream_t st)
 {
     const dim3 grid(sd_blocks(b.total)), blk(kSdBlock);
     hipLaunchKernelGGL(sd_bind_find, grid, blk, 0, st, b);
     hipLaunchKernelGGL(sd_bind_flag, grid, blk, 0, st, b);
     if (int rc = sd_launched()) return rc;
-    if (int rc = rg::rg_scan(b.rank, b.total, sums, b.w + kNew, st)) return rc;
+    return rg::rg_scan(b.rank, b.total, sums, b.w + kNew, st);
+}
+
+inline int sd_bind_back(const SdBind &b, uint32_t *d_counts, hipStream_t st)
+{
+    const dim3 grid(sd_blocks(b.total)), blk(kSdBlock);
     hipLaunchKernelGGL(sd_bind_assign, grid, blk, 0, st, b);
     hipLaunchKernelGGL(sd_bind_answer, grid, blk, 0, st, b);
     hipLaunchKernelGGL(sd_bind_finish, dim3(1), dim3(64), 0, st, b.w, b.n, d_counts);
@@ -448,6 +466,10 @@ struct SdDir {
     size_t bind_cap = 0, rel_cap = 0;
     bool bind_dirty = false; // a bind failed part way: its scratch table is cleared before the next
     uint64_t tomb_bound = 0; // no more tombstones than this are in the table
+    // use stamps (mk_session_dir_track, sess_evict.h): null until tracked
+    void *d_ev = nullptr;     // last[n] first, then the selection's scratch
+    uint64_t *last = nullptr;
+    uint64_t clock = 0;       // binds queued since tracking began
 };
 
 inline size_t sd_dir_carve(SdDir *d, size_t n, void *base)
@@ -468,6 +490,7 @@ inline void sd_dir_free(SdDir *d)
     (void)hipFree(d->d_base);
     (void)hipFree(d->d_bind);
     (void)hipFree(d->d_rel);
+    (void)hipFree(d->d_ev);
     (void)hipHostFree(d->h_w);
     delete d;
 }

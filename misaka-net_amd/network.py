@@ -84,6 +84,8 @@ class BatchResult:
     rounds: Optional[int] = None  # SessionSet.serve: ragged launches made
     ids: Optional[np.ndarray] = None  # SessionDirectory: uint32, the instance of each request (0xffffffff: none)
     counts: Optional[tuple] = None  # SessionDirectory: keys admitted, keys rejected, requests of rejected keys
+    evicted_keys: Optional[np.ndarray] = None  # SessionDirectory with evict: the victims' keys (then counts[3]: their number)
+    evicted_ids: Optional[np.ndarray] = None  # and their instances, increasing
 
     @property
     def has_output(self) -> np.ndarray:
@@ -921,18 +923,116 @@ class SessionDirectory:
             raise ValueError(f"keys position {t}: {k.size} keys for {v.size} values (len(keys) != len(values))")
         return k, np.ascontiguousarray(v)
 
-    def bind(self, keys):
+    def bind(self, keys, evict=None, min_idle=1):
         """The instance of every key, in arrival order, new keys admitted
         (mk_session_bind): ``(ids, counts)`` -- uint32 ids, 0xffffffff for
         :data:`KEY_NONE` and for a key rejected because no instance was free,
         and ``counts = (keys admitted, keys rejected, requests of rejected
         keys)``.  New keys take the free instances in the order of their first
-        occurrence."""
+        occurrence.
+
+        With ``evict`` (a tracked directory, :meth:`track`) the bind makes
+        room: when the new keys outnumber the free instances, up to ``evict``
+        of the clients silent longest -- at least ``min_idle`` binds, no call
+        open -- are evicted first (mk_session_bind_evict).  The result is then
+        ``(ids, counts, evicted_keys, evicted_ids)`` with the number evicted as
+        ``counts[3]`` and the victims in increasing instance order."""
         k = self._keys(keys)
         ids = np.zeros(k.size, np.uint32)
-        c = (C.c_size_t * 3)()
-        N.check(N.lib().mk_session_bind(self._h, _ptr(k), k.size, _ptr(ids), c), "mk_session_bind")
-        return ids, tuple(int(x) for x in c)
+        if evict is None:
+            c = (C.c_size_t * 3)()
+            N.check(N.lib().mk_session_bind(self._h, _ptr(k), k.size, _ptr(ids), c), "mk_session_bind")
+            return ids, tuple(int(x) for x in c)
+        want, idle = self._want("evict", evict), self._want("min_idle", min_idle)
+        cap = min(want, self._set.n)
+        ek, ei = np.full(cap, KEY_NONE, np.uint64), np.full(cap, NO_INSTANCE, np.uint32)
+        c = (C.c_size_t * 4)()
+        N.check(N.lib().mk_session_bind_evict(self._h, _ptr(k), k.size, _ptr(ids), want, idle, _ptr(ek), _ptr(ei), c),
+                "mk_session_bind_evict")
+        return ids, tuple(int(x) for x in c), ek[:c[3]], ei[:c[3]]
+
+    @staticmethod
+    def _want(name, value):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+            raise ValueError(f"{name} = {value!r} is not an integer")
+        if not 0 <= int(value) < 1 << 32:
+            raise ValueError(f"{name} = {value} outside [0, 2^32)")
+        return int(value)
+
+    def track(self):
+        """Turn use tracking on (mk_session_dir_track): from now on every bind
+        stamps the instances it resolves to with the directory's clock, the
+        number of binds so far.  ValueError on a second call."""
+        rc = N.lib().mk_session_dir_track(self._h)
+        if rc == N.MK_EINVAL:
+            raise ValueError("this directory is tracked already")
+        N.check(rc, "mk_session_dir_track")
+
+    def use_info(self) -> "N.mk_session_dir_use_info":
+        """``clock`` and ``tracking`` of the directory."""
+        i = N.mk_session_dir_use_info()
+        N.check(N.lib().mk_session_dir_use_info_get(self._h, C.byref(i)), "mk_session_dir_use_info_get")
+        return i
+
+    def _select(self, name, want, min_idle):
+        want, idle = self._want("want", want), self._want("min_idle", min_idle)
+        cap = min(want, self._set.n)
+        keys, ids = np.full(cap, KEY_NONE, np.uint64), np.full(cap, NO_INSTANCE, np.uint32)
+        c = C.c_size_t()
+        N.check(getattr(N.lib(), name)(self._h, want, idle, _ptr(keys), _ptr(ids), C.byref(c)), name)
+        return keys[:c.value], ids[:c.value]
+
+    def idle(self, want, min_idle=1):
+        """The ``want`` clients silent longest (mk_session_idle_select):
+        ``(keys, ids)`` in increasing instance order, fewer when fewer are
+        eligible -- bound, at least ``min_idle`` binds since the last one that
+        named them, no call open.  Changes nothing.  To park them:
+        ``snapshot(index=ids)``, then ``release(keys)``."""
+        return self._select("mk_session_idle_select", want, min_idle)
+
+    def evict(self, want, min_idle=1):
+        """:meth:`idle`, and the selected clients are released
+        (mk_session_evict): ``(keys, ids)`` of the victims."""
+        return self._select("mk_session_evict", want, min_idle)
+
+    def export_use(self):
+        """``(last, clock)``: the use stamp of every instance (uint64, 0 for a
+        free one) and the directory's clock."""
+        last = np.zeros(self._set.n, np.uint64)
+        clock = C.c_uint64()
+        N.check(N.lib().mk_session_dir_use_export(self._h, _ptr(last), C.byref(clock)), "mk_session_dir_use_export")
+        return last, clock.value
+
+    def load_use(self, last, clock):
+        """Replace the use stamps and the clock by what :meth:`export_use`
+        gave (after :meth:`load`).  ValueError, with nothing changed, when a
+        bound instance has a stamp above ``clock``."""
+        a = np.ascontiguousarray(np.asarray(last, dtype=np.uint64).reshape(-1))
+        if a.size != self._set.n:
+            raise ValueError(f"last position {min(a.size, self._set.n)}: {a.size} stamps for {self._set.n} instances")
+        if not 0 <= clock < 1 << 64:
+            raise ValueError(f"clock = {clock} outside [0, 2^64)")
+        rc = N.lib().mk_session_dir_use_import(self._h, _ptr(a), clock)
+        if rc == N.MK_EINVAL:
+            raise ValueError("untracked, or a stamp above the clock: nothing loaded")
+        N.check(rc, "mk_session_dir_use_import")
+
+    def _evicting(self, form, keys, values, evict, min_idle, **kw):
+        """bind_evict, then the unkeyed ``form`` on the requests that got an
+        instance; the others report 0 / 0 / 0."""
+        k, v = self._keys(keys, values)
+        ids, counts, ek, ei = self.bind(k, evict=evict, min_idle=min_idle)
+        got = ids != NO_INSTANCE
+        steps = kw.get("steps", True)
+        r = BatchResult(np.zeros(k.size, np.int32), np.zeros(k.size, np.uint8),
+                        np.zeros(k.size, np.uint32) if steps else None)
+        part = getattr(self._set, form)(ids[got], v[got], **kw)
+        r.out[got], r.status[got] = part.out, part.status
+        if steps:
+            r.steps[got] = part.steps
+        r.still_open, r.rounds = part.still_open, part.rounds
+        r.ids, r.counts, r.evicted_keys, r.evicted_ids = ids, counts, ek, ei
+        return r
 
     def lookup(self, keys) -> np.ndarray:
         """As :meth:`bind`, but nothing is admitted: an unbound key gives
@@ -951,11 +1051,17 @@ class SessionDirectory:
         N.check(N.lib().mk_session_release(self._h, _ptr(k), k.size, C.byref(r)), "mk_session_release")
         return r.value
 
-    def compute_queue(self, keys, values, *, steps=True, busy_ok=False) -> BatchResult:
+    def compute_queue(self, keys, values, *, steps=True, busy_ok=False, evict=None, min_idle=1) -> BatchResult:
         """:meth:`bind`, then :meth:`SessionSet.compute_queue` on the ids, in
         one call with the keys staged once (mk_session_compute_queue_keyed).
         The result also carries ``ids`` and ``counts``; the requests of
-        rejected keys and of :data:`KEY_NONE` report 0 / 0 / 0."""
+        rejected keys and of :data:`KEY_NONE` report 0 / 0 / 0.  With
+        ``evict`` the bind makes room as :meth:`bind` describes (two calls:
+        mk_session_bind_evict, then the unkeyed queue on the ids), and the
+        result carries ``evicted_keys`` and ``evicted_ids`` too."""
+        if evict is not None:
+            return self._evicting("compute_queue", keys, values, evict, min_idle, steps=steps,
+                                  busy_ok=busy_ok)
         k, v = self._keys(keys, values)
         ids = np.zeros(k.size, np.uint32)
         c = (C.c_size_t * 3)()
@@ -964,10 +1070,14 @@ class SessionDirectory:
         r.ids, r.counts = ids, tuple(int(x) for x in c)
         return r
 
-    def serve(self, keys, values, *, max_slices=16, steps=True, busy_ok=False, promote=False) -> BatchResult:
+    def serve(self, keys, values, *, max_slices=16, steps=True, busy_ok=False, promote=False, evict=None,
+              min_idle=1) -> BatchResult:
         """:meth:`bind`, then :meth:`SessionSet.serve` on the ids
         (mk_session_serve_keyed); the result also carries ``ids`` and
-        ``counts``."""
+        ``counts``.  ``evict`` as in :meth:`compute_queue`."""
+        if evict is not None:
+            return self._evicting("serve", keys, values, evict, min_idle, max_slices=max_slices, steps=steps,
+                                  busy_ok=busy_ok, promote=promote)
         n = SessionSet._slices("max_slices", max_slices)
         k, v = self._keys(keys, values)
         ids = np.zeros(k.size, np.uint32)
@@ -1024,6 +1134,31 @@ class SessionDirectory:
         :meth:`SessionSet.compute_queue_device` and ``serve_device`` as they are."""
         N.check(N.lib().mk_session_bind_device(self._h, keys_ptr, self._total(total), ids_ptr, counts_ptr, stream),
                 "mk_session_bind_device")
+
+    def bind_evict_device(self, keys_ptr, total, ids_ptr, max_evict, *, min_idle=1, ev_keys_ptr=None, ev_ids_ptr=None,
+                          counts_ptr=None, stream=None):
+        """:meth:`bind` with ``evict`` on device arrays, asynchronous on
+        ``stream`` (mk_session_bind_evict_device): the victims' lists take
+        ``min(max_evict, n)`` entries each (or None), ``counts_ptr`` four
+        uint32 words (or None)."""
+        N.check(N.lib().mk_session_bind_evict_device(self._h, keys_ptr, self._total(total), ids_ptr,
+                                                     self._want("max_evict", max_evict),
+                                                     self._want("min_idle", min_idle), ev_keys_ptr, ev_ids_ptr,
+                                                     counts_ptr, stream), "mk_session_bind_evict_device")
+
+    def idle_device(self, want, keys_ptr, ids_ptr, count_ptr=None, *, min_idle=1, stream=None):
+        """:meth:`idle` into device arrays of ``min(want, n)`` entries each,
+        padded; ``count_ptr`` (one device uint32, or None) takes the number
+        (mk_session_idle_select_device)."""
+        N.check(N.lib().mk_session_idle_select_device(self._h, self._want("want", want),
+                                                      self._want("min_idle", min_idle), keys_ptr, ids_ptr, count_ptr,
+                                                      stream), "mk_session_idle_select_device")
+
+    def evict_device(self, want, keys_ptr=None, ids_ptr=None, count_ptr=None, *, min_idle=1, stream=None):
+        """:meth:`evict` on the device, asynchronous on ``stream``; every array
+        may be None (mk_session_evict_device)."""
+        N.check(N.lib().mk_session_evict_device(self._h, self._want("want", want), self._want("min_idle", min_idle),
+                                                keys_ptr, ids_ptr, count_ptr, stream), "mk_session_evict_device")
 
     def lookup_device(self, keys_ptr, total, ids_ptr, *, stream=None):
         """:meth:`lookup` on device arrays, asynchronous on ``stream``."""
